@@ -5,9 +5,13 @@
 
 A "step" is one pass of the hot path (GameEnv.step: 12 physics sub-steps + reward + observation + done,
 reference RR_EnvBase.py:260-297) over one batch of 65,536 arenas per GPU.  Metric = BASELINE.json's
-env-steps/s (whole job).  Inputs (state, actions) are resident in HBM when the timed region starts.
-Rank 0 prints ONE JSON line, with `roofline` (dominant kernel vs the HBM roof) and `cpu_baseline`
+env-steps/s (whole job).  Inputs (state, actions) are resident in HBM when the timed region starts, and are the same from
+run to run for the same arguments (every generator is seeded).
+Rank 0 prints ONE JSON line, with `roofline` (dominant kernel vs the HBM roof, from the timed steps' own events).
+A plain run does only what that line needs.  --full adds the figures that take runs of their own: `from_reset` (K steps
+timed right after a fresh reset, before the pre-roll), `roofline.peak_measured*` (an HBM copy probe) and `cpu_baseline`
 (the CPU oracle timed on this box's host cores on a bounded sample -- a reported baseline, not the target).
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -47,9 +51,37 @@ def parse():
     ap.add_argument("--no-stagger", action="store_true", help="time the steps right after a fresh reset (every arena at the same, "
                     "contact-poor episode phase).  Default: arenas at uniformly random episode phases, reached by a pre-roll of "
                     "one whole episode outside the timed region -- the steady state of a long rollout")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true", help="also measure the secondary figures, each outside the timed region: "
+                    "from_reset, the HBM copy probe (roofline.peak_measured*) and cpu_baseline.  Off: the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave cpu_baseline out")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: wall time of the CPU baseline's sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the arrays the last timed step returned "
+                    "as DIR/<name>.npy (float32; status in float64)")
     return ap.parse_args()
+
+
+DUMP_NAMES = ("obs", "reward", "done", "grumpy_obs", "grumpy_score", "status")  # env.step's obs, reward, done, info.*
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, outs, suffix=""):
+    """--dump-outputs: the six arrays a caller of the timed step receives (out tuple order: obs, reward, done, grumpy_obs,
+    grumpy_score, status; grumpy_obs is None without a grumpy team) as DIR/<name><suffix>.npy, status in float64 (its bits
+    exactly), the rest in float32.  Should the whole exceed 64 MB, every array keeps the same fixed, seeded sample of arena rows,
+    whose indices go to arena_rows<suffix>.npy."""
+    import numpy as np
+    arrs = {k: t.detach().cpu().numpy().astype(np.float64 if k == "status" else np.float32)
+            for k, t in zip(DUMP_NAMES, outs) if t is not None}
+    n = arrs["obs"].shape[0]
+    row_bytes = sum(v[:1].nbytes for v in arrs.values())
+    if n * row_bytes > DUMP_MAX_BYTES:
+        m = (DUMP_MAX_BYTES - 4096 * len(DUMP_NAMES)) // (row_bytes + 8)  # room for the .npy headers and arena_rows
+        rows = np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+        arrs = {k: v[rows] for k, v in arrs.items()}
+        arrs["arena_rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), v)
 
 
 def maybe_relaunch(args):
@@ -181,6 +213,9 @@ def pipelined(args):
     cnt1 = sum(int(e.episode_stats()[3].sum().item()) for e in pipe.envs)
     resets = cnt1 - cnt0 - sum(int(o[2].sum().item()) for o in outs)
     n_not_ready = sum(int(((h & 16384) != 0).sum().item()) for h in hist) if args.budget else 0
+    if args.dump_outputs:  # the shards' last step, in global arena order
+        last = [outs[i][:5] + ((hist[i][K - 1],) if args.budget else (outs[i][5],)) for i in range(P)]
+        dump_outputs(args.dump_outputs, [torch.cat([s[k] for s in last]) if last[0][k] is not None else None for k in range(6)])
     steps = N * K - max(resets, 0) - n_not_ready
     bytes_per_step = p.algorithmic_bytes_per_step(na)
     achieved = bytes_per_step * steps / dt / 1e9
@@ -248,7 +283,7 @@ def main():
 
     stagger = not args.no_stagger and args.fuse == 1
     from_reset = None
-    if stagger and args.policy == "random" and not args.budget and K + W < p.game_len_steps:
+    if args.full and stagger and args.policy == "random" and not args.budget and K + W < p.game_len_steps:
         # secondary number, same run: the K steps right after a fresh reset (what rounds 1-2 reported as the headline: every
         # arena at the same, contact-poor start of its episode) -- kept so that the lines stay comparable across rounds
         for i in range(W):
@@ -335,6 +370,9 @@ def main():
     n_not_ready = int(((status_hist & 16384) != 0).sum().item()) if args.budget else 0
     if args.budget:
         out = out[:5] + (status_hist[K - 1],)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [t[-1] if t is not None else None for t in fout] if F > 1 else out,
+                     suffix=f"_rank{rank}" if world > 1 else "")
     local_steps = n * K - max(resets, 0) - n_not_ready
     total_steps = rrd.reduce_sum(float(local_steps), dev)
     kern_ms = sum(ev[i][0].elapsed_time(ev[i][1]) for i in range(0, K, F)) / (K // F)  # per launch
@@ -357,8 +395,6 @@ def main():
                 traffic = None
         if traffic_source:
             traffic_source += "; a constant from that profiling run, not measured by this bench run"
-        peak_kernel, peak_torch = hbm_copy_probe(dev)
-        peak_measured = max(peak_kernel, peak_torch)
         line = {
             "metric": "env_steps_per_sec", "value": total_steps / dt, "unit": "env-steps/s", "n_gpus": world,
             "steps": K, "warmup": W, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -386,18 +422,21 @@ def main():
                                        "every_steps": gather_every} if world > 1 else None},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "peak_measured": peak_measured,
-                         "peak_measured_how": "device-to-device copy of 1 GiB, read + write bytes / HIP-event time, this run: the better of the "
-                                              "library's one-16-B-element-per-thread copy kernel (rr_probe_hbm_copy) and torch's copy_",
-                         "peak_measured_copy_kernel": peak_kernel, "peak_measured_torch_copy": peak_torch,
                          "kernel": "k_step", "kernel_ms": kern_ms, "algorithmic_bytes_per_env_step": bytes_per_step,
                          "record_bytes_per_env": env.state_bytes_per_env(),
                          "note": "latency/VALU-bound by construction: 12 dependent sub-steps of fp64 geometry per "
                                  "149-601 B of state; the HBM fraction is reported because BASELINE.json asks for it"},
         }
+        if args.full:
+            peak_kernel, peak_torch = hbm_copy_probe(dev)
+            line["roofline"].update({
+                "peak_measured": max(peak_kernel, peak_torch),
+                "peak_measured_how": "device-to-device copy of 1 GiB, read + write bytes / HIP-event time, this run: the better of the "
+                                     "library's one-16-B-element-per-thread copy kernel (rr_probe_hbm_copy) and torch's copy_",
+                "peak_measured_copy_kernel": peak_kernel, "peak_measured_torch_copy": peak_torch})
         if from_reset is not None:
             line["from_reset"] = from_reset
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(args.preset, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     rrd.barrier()

@@ -118,10 +118,10 @@ def test_config4_shape_eight_shards_of_65536_equal_one_batch_of_524288():
 
 @pytest.mark.timeout(600)
 def test_bench_single_gpu_line_carries_roofline_and_cpu_baseline():
-    """bench.py as the driver runs it at N = 1 (short): ONE JSON line with the contract's keys, the roofline object of the
+    """bench.py --full at N = 1 (short): ONE JSON line with the contract's keys, the roofline object of the
     dominant kernel and the cpu_baseline object (the oracle timed on this box's host cores)."""
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--cpu-seconds", "2"],
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=540, cwd=REPO)
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--cpu-seconds", "2",
+                        "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=540, cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -139,6 +139,34 @@ def test_bench_single_gpu_line_carries_roofline_and_cpu_baseline():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "env-steps/s" and cb["cores"] >= 1 and cb["value"] > 100 and "sample" in cb
     assert abs(d["value"] - 65536 * 10 / (d["ms_per_step"] * 10e-3)) / d["value"] < 0.02
+    assert rf["peak_measured"] > 0 and d["from_reset"]["value"] > 0
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_line_is_lean_and_its_dumped_outputs_repeat(tmp_path):
+    """bench.py without --full: the headline line without the figures that take runs of their own, and --dump-outputs writes the
+    last timed step's arrays -- the same ones in two runs with the same arguments."""
+    n = 4096
+    lines = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--arenas",
+                            str(n), "--dump-outputs", str(tmp_path / run)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=270, cwd=REPO)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines += [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 2
+    for d in lines:
+        assert d["steps"] == 10 and d["warmup"] == 3 and d["dtype"] == "f64" and d["ms_per_step"] > 0
+        assert abs(d["value"] - n * 10 / (d["ms_per_step"] * 10e-3)) / d["value"] < 0.02
+        assert "cpu_baseline" not in d and "from_reset" not in d and "peak_measured" not in d["roofline"]
+    import numpy as np
+    shapes = {"obs": (n, 11), "reward": (n,), "done": (n,), "grumpy_obs": (n, 11), "grumpy_score": (n,), "status": (n,)}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in shapes)
+    for k, shape in shapes.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.shape == shape and a.dtype == (np.float64 if k == "status" else np.float32), k
+        assert np.array_equal(a, b, equal_nan=True), k
+    assert np.isin(np.load(tmp_path / "a" / "done.npy"), (0.0, 1.0)).all()
 
 
 @pytest.mark.timeout(600)

@@ -13,8 +13,8 @@ rc=$?
 tail -n 40 $OUT/pytest.log
 echo "pytest exit code $rc"
 if [ $rc -ge 124 ]; then echo "pytest hung or was killed: no further GPU step"; exit $rc; fi
-timeout -k 10 300 python bench.py --steps 200 --warmup 20 > $OUT/bench_G_f64.json 2> $OUT/bench_G_f64.err || { echo "bench G failed"; tail -5 $OUT/bench_G_f64.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 > $OUT/bench_G_f64.json 2> $OUT/bench_G_f64.err || { echo "bench G failed"; tail -5 $OUT/bench_G_f64.err; exit 1; }
 cat $OUT/bench_G_f64.json
-timeout -k 10 300 python bench.py --preset T --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_T_f64.json 2> $OUT/bench_T_f64.err || { echo "bench T failed"; exit 1; }
+timeout -k 10 300 python bench.py --preset T --steps 200 --warmup 20 --full --no-cpu-baseline > $OUT/bench_T_f64.json 2> $OUT/bench_T_f64.err || { echo "bench T failed"; exit 1; }
 cat $OUT/bench_T_f64.json
 exit $rc

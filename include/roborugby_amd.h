@@ -119,7 +119,8 @@ int rr_step(rr_env *env, const int32_t *actions, int32_t na, float *obs, float *
 int rr_step_f64(rr_env *env, const int32_t *actions, int32_t na, double *obs, double *reward, uint8_t *done,
                 double *obs_g, double *reward_g, int32_t *status, void *stream);
 /* Changes rr_config.step_budget_clocks of a live handle (host-side; takes effect with the next rr_step).  0 switches parking
- * off -- arenas that are parked at that moment finish their step in the next call(s) as usual. */
+ * off -- arenas that are parked at that moment finish their step in the next call(s) as usual.  Any value may be set while
+ * arenas are parked: they go on with their step under the new budget; their observation rows are not touched. */
 int rr_set_step_budget(rr_env *env, uint32_t clocks);
 /* Open-loop rollout: nsteps consecutive rr_step calls per arena in ONE launch -- the record stays in LDS, and no arena
  * waits for the slowest arena of the batch between steps (a launch per step ends when its slowest wavefront does).
@@ -182,7 +183,11 @@ int rr_set_episode_state(rr_env *env, const int32_t *ints, const double *acc, vo
  * Reward keepers, given in on_step_end EXECUTION order (each keeper calls super() first, except NaughtyBots which
  * never does, so keepers behind it in the MRO do not run): 1 NaughtyBots, 2 ChasePosBall, 3 PushPosBallsToGoal,
  * 4 DontDriveInGoals, 5 KeepMovingGuys, 6 BaseDestruction, 7 PushNegBallsFromGoal (RR_ScoreKeepers.py:46-179).
- * Default {1,2,3}.  n <= 8. */
+ * Default {1,2,3}.  n <= 8.
+ * Budgeted step: a switch takes effect with the steps that complete from the next call on -- a parked arena's step is scored by
+ * the new program from the on_step_begin copies taken when that step began.  Those copies are only kept while a non-default
+ * program or rr_track_prior_step is on: a switch from the default program with tracking off, while some arena is parked, returns
+ * -1 and changes nothing (rr_set_step_budget(env, 0) and one rr_step first: no arena is parked then). */
 int rr_set_reward_program(rr_env *env, const int32_t *keeper_ids, int32_t n);
 /* Observers: kind 0 SingleBall_6wayLidar_v2 (11 values), 1 SingleBall_6wayLidar (11, RR_Observers.py:168-285),
  * 2 PosBall_BasicLidar (5, :116-166), 3 AllCoords (3*NR + 2*NB, :47-83), 4 AllCoords_WithPrior (6*NR + 4*NB, :86-110:
@@ -196,7 +201,9 @@ int rr_observe_kind_f64(rr_env *env, int32_t kind, int32_t team, int32_t robot_i
 
 /* on != 0: every rr_step / rr_step_thrust first snapshots what the sprites' on_step_begin copies (rectDblPriorStep,
  * RR_Robot.py:116-117, RR_Ball.py:60-61) so that observer kind 4 can report it; the call itself (and rr_reset) seeds the
- * copies from the current poses (the reference holds the stale pre-placement pose until the first step). */
+ * copies from the current poses (the reference holds the stale pre-placement pose until the first step).
+ * Budgeted step: a parked arena keeps the copies of its step begin.  Switching on while the default keeper program is set and some
+ * arena is parked returns -1 and changes nothing -- no copies were kept when those steps began (see rr_set_reward_program). */
 int rr_track_prior_step(rr_env *env, int32_t on, void *stream);
 
 /* Opt-in goal scoring -- an EXTENSION: on the reference's live path the goals never score (Goal.track_balls / update_score are

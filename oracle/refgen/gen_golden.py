@@ -530,6 +530,10 @@ def gen_kat(R, preset):
 
 # ------------------------------------------------------------------ reset layouts
 def gen_reset(R, preset, n=1000):
+    # The constructor places the arena too, and the first reset's placement tries its candidates against that layout (robots not yet
+    # re-placed still block at their old poses): unseeded, one run in a few dozen drew a layout that rejected a candidate of episode 0
+    # and shifted its draws.  Seeded, the layout blocks nothing and the file is the one committed.
+    random.seed(999)
     env = R.envs.SimpleDuel3()
     rob, bal, obs = [], [], []
     for k in range(n):

@@ -283,6 +283,13 @@ __global__ void k_goal(SimParams<typename C::Real> sp, typename C::Store *recs, 
     goal_step<C, O>(recs + (size_t)a * Arena<C>::P_STRIDE, irecs + (size_t)a * Arena<C>::I_STRIDE, sp, gs + (size_t)a * gs_stride<C>(),
                     base_destruction != 0, reward + a, reward_g ? reward_g + a : nullptr, done + a, status + a);
 }
+// budgeted step: is some arena parked mid-step (bit 31 of its record's fzp word, as k_extras_begin reads it)?  Setters only.
+template <class C>
+__global__ void k_any_parked(const int32_t *irecs, int n, int32_t *flag) {
+    int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n) return;
+    if (irecs[(size_t)a * Arena<C>::I_STRIDE + 3 * C::NR + 6] < 0) *flag = 1;
+}
 template <class C>
 __global__ void k_goal_clear(int n, int32_t *gs, const uint8_t *mask) {
     int a = blockIdx.x * blockDim.x + threadIdx.x;
@@ -360,6 +367,7 @@ struct rr_env {
     int ngroups;
     uint32_t *park;      // parked mid-step state of the budgeted step (null until a budget is first set)
     uint32_t budget;     // shader clocks; 0xFFFFFFFF = "no budget, but parked arenas may exist" (after the budget was switched off)
+    int32_t *flag;       // one word for any_parked (lazy)
 };
 
 static thread_local std::string g_err;
@@ -448,7 +456,7 @@ int rr_create(const rr_config *cfg, rr_env **out) {
     e->vw = 0;
     e->prog.n = 3; e->prog.id[0] = KEEPER_NAUGHTY; e->prog.id[1] = KEEPER_CHASE; e->prog.id[2] = KEEPER_PUSHPOS;
     e->custom_prog = false; e->track_prior = false; e->xs = nullptr; e->status_buf = nullptr; e->gs = nullptr;
-    e->park = nullptr; e->budget = 0;
+    e->park = nullptr; e->budget = 0; e->flag = nullptr;
     const char *want = getenv("RR_VW");
     const int want_vw = want ? atoi(want) : 0;
 #define X(kind_, a, b, c, d, R_, vw_) \
@@ -536,6 +544,7 @@ int rr_destroy(rr_env *e) {
     if (e->order) (void)hipFree(e->order);
     if (e->cost) (void)hipFree(e->cost);
     if (e->park) (void)hipFree(e->park);
+    if (e->flag) (void)hipFree(e->flag);
     delete e;
     return 0;
 }
@@ -657,7 +666,45 @@ static int ensure_snapshot_buffer(rr_env *e) { // on_step_begin snapshot of ever
     if (e->xs) return 0;
     const size_t rsz = e->cfg.dtype == RR_DTYPE_F32 ? 4 : 8; // (arithmetic reals)
     const size_t nr = (size_t)(e->cfg.nr_happy + e->cfg.nr_grumpy), nb = (size_t)(e->cfg.nb_pos + e->cfg.nb_neg);
-    HIP_TRY(hipMalloc(&e->xs, rsz * (3 * nr + 1 + 2 * nb) * (size_t)e->cfg.num_envs));
+    const size_t bytes = rsz * (3 * nr + 1 + 2 * nb) * (size_t)e->cfg.num_envs;
+    HIP_TRY(hipMalloc(&e->xs, bytes));
+    HIP_TRY(hipMemset(e->xs, 0, bytes));
+    return 0;
+}
+
+// Budgeted step: whether some arena is parked mid-step -- after the work queued on `stream` (one small kernel + a synchronous copy;
+// setters only, never the step path).  A handle that never had a budget has none.
+static int any_parked(rr_env *e, void *stream, bool &parked) {
+    parked = false;
+    if (!e->park) return 0;
+    const int n = e->cfg.num_envs;
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->flag) HIP_TRY(hipMalloc((void **)&e->flag, sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(e->flag, 0, sizeof(int32_t), s));
+    int rc = dispatch(e, [&](auto c) {
+        using CC = decltype(c);
+        hipLaunchKernelGGL((k_any_parked<CC>), dim3((n + 127) / 128), dim3(128), 0, s, (const int32_t *)e->irecs, n, e->flag);
+        return 0;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    int32_t h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, e->flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    parked = h != 0;
+    return 0;
+}
+// A custom keeper program and prior-step tracking read the on_step_begin copies k_extras_begin takes at the start of an arena's step.
+// When neither was on, no copies were taken for the steps that parked arenas are in the middle of: switching either on then would score
+// / observe those steps from whatever the buffer holds, so the switch is refused (nothing changes) until no arena is parked.  When one
+// of them was on, the parked arenas keep the copies of their step begin and the switch is synchronous-equivalent.
+static int refuse_if_parked_without_copies(rr_env *e, void *stream, const char *who) {
+    if (e->custom_prog || e->track_prior || !e->park) return 0;
+    bool parked = false;
+    if (int rc = any_parked(e, stream, parked)) return rc;
+    if (parked)
+        return fail(-1, std::string(who) + ": arenas are parked mid-step (budgeted step) and no on_step_begin copies were kept when their "
+                                           "step began; rr_set_step_budget(env, 0) and one rr_step complete every parked step first");
     return 0;
 }
 
@@ -667,9 +714,14 @@ int rr_set_reward_program(rr_env *e, const int32_t *ids, int32_t n) {
     for (int i = 0; i < n; i++)
         if (ids[i] < KEEPER_NAUGHTY || ids[i] > KEEPER_PUSHNEG) return fail(-1, "rr_set_reward_program: unknown keeper id");
     DeviceGuard guard(e->cfg.device);
+    const bool custom = !(n == 3 && ids[0] == KEEPER_NAUGHTY && ids[1] == KEEPER_CHASE && ids[2] == KEEPER_PUSHPOS);
+    if (custom && !e->custom_prog && !e->track_prior && e->park) {
+        HIP_TRY(hipDeviceSynchronize()); // (no stream argument: the steps queued before this call, on any stream, come first)
+        if (int rc = refuse_if_parked_without_copies(e, nullptr, "rr_set_reward_program")) return rc;
+    }
     e->prog.n = n;
     for (int i = 0; i < n; i++) e->prog.id[i] = ids[i];
-    e->custom_prog = !(n == 3 && ids[0] == KEEPER_NAUGHTY && ids[1] == KEEPER_CHASE && ids[2] == KEEPER_PUSHPOS);
+    e->custom_prog = custom;
     e->spd.acc_external = e->spf.acc_external = e->custom_prog ? 1 : 0; // k_extras_end keeps the episode returns then
     if (e->custom_prog) { // allocated here, never inside rr_step (keeps the step launch-only)
         if (int rc = ensure_snapshot_buffer(e)) return rc;
@@ -737,6 +789,9 @@ int rr_goal_scores(rr_env *e, int32_t *scores, void *stream) {
 int rr_track_prior_step(rr_env *e, int32_t on, void *stream) {
     if (!e) return fail(-1, "rr_track_prior_step: null handle");
     DeviceGuard guard(e->cfg.device);
+    if (on && !e->track_prior) {
+        if (int rc = refuse_if_parked_without_copies(e, stream, "rr_track_prior_step")) return rc;
+    }
     e->track_prior = on != 0;
     if (!e->track_prior) return 0;
     if (int rc = ensure_snapshot_buffer(e)) return rc;

@@ -220,19 +220,31 @@ class BatchedRoboRugbyEnv:
     def _new(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
 
-    def _seed_bout(self):
-        """Budgeted mode: the persistent step outputs, with both teams' observation rows holding the CURRENT observation -- a row
-        that is NOT_READY in the next step() is not written by the kernel and must read as the arena's previous observation
-        (called wherever a budget is switched on or the arenas are rewritten from outside: reset, set_state, set_poses)."""
+    def _seed_bout(self, mask=None, obs=None):
+        """Budgeted mode: the persistent step outputs, with both teams' observation rows of the arenas in `mask` (None: all) set to
+        the CURRENT observation -- a row that is NOT_READY in the next step() is not written by the kernel and must read as the
+        arena's previous observation.  Called when the first budget is set and for the rows of arenas rewritten from outside (all of
+        them after set_state / set_poses / reset(), the masked ones after reset(mask), which passes the happy rows it returns as
+        `obs`); the other rows keep what step() handed out: a parked arena's record holds the middle of its step, not an observation."""
         N = self.num_envs
         if self._bout is None:
             self._bout = (self._new((N, 11), torch.float32), torch.zeros(N, dtype=torch.float32, device=self.device),
                           torch.zeros(N, dtype=torch.uint8, device=self.device),
                           self._new((N, 11), torch.float32) if self.has_grumpy else None,
                           torch.zeros(N, dtype=torch.float32, device=self.device), torch.zeros(N, dtype=torch.int32, device=self.device))
-        _lib.check(self._lib.rr_observe(self._h, 1, -1, -1, _ptr(self._bout[0]), self._stream()), "rr_observe", self._lib)
-        if self.has_grumpy:
-            _lib.check(self._lib.rr_observe(self._h, -1, -1, -1, _ptr(self._bout[3]), self._stream()), "rr_observe", self._lib)
+            mask = None
+        for team, rows in ((1, self._bout[0]), (-1, self._bout[3])):
+            if rows is None:
+                continue
+            if team == 1 and obs is not None:
+                cur = obs
+            else:
+                cur = rows if mask is None else self._new((N, 11), torch.float32)
+                _lib.check(self._lib.rr_observe(self._h, team, -1, -1, _ptr(cur), self._stream()), "rr_observe", self._lib)
+            if mask is not None:
+                rows.copy_(torch.where(mask.view(N, 1).bool(), cur, rows))
+            elif cur is not rows:
+                rows.copy_(cur)
 
     # ---------------------------------------------------------------- gym surface
     def _reset_to_start(self, mask, obs):
@@ -254,19 +266,25 @@ class BatchedRoboRugbyEnv:
     def reset(self, mask=None, *, bln_randomize_pos=True):
         """env.reset(bln_randomize_pos) (RR_EnvBase.py:202-216) for all arenas, or those where mask is True: a fresh random
         placement (_set_random_positions), or with bln_randomize_pos=False the start configuration kept since construction
-        (_set_starting_positions, RR_EnvBase.py:131-153; main.py:107 replays its layout that way)."""
+        (_set_starting_positions, RR_EnvBase.py:131-153; main.py:107 replays its layout that way).
+        Budgeted mode: an arena in the mask that is parked loses the rest of its step (like set_state); the rows outside the mask
+        are each arena's previous observation -- for a parked arena the one the last step() without `out` handed out -- and the
+        NOT_READY rows of the next step() keep them."""
         N = self.num_envs
         obs = self._new((N, 11), torch.float32)
         mask = self._mask(mask)
         if mask is not None:
-            # rows that are not reset keep their current observation
+            # rows that are not reset keep their current observation; a parked arena has none (its record is mid-step)
             _lib.check(self._lib.rr_observe(self._h, 1, -1, -1, _ptr(obs), self._stream()), "rr_observe", self._lib)
+            if self._bout is not None:
+                parked = (self._bout[5] & STATUS_NOT_READY) != 0
+                obs = torch.where(parked.view(N, 1), self._bout[0], obs).contiguous()
         if bln_randomize_pos:
             _lib.check(self._lib.rr_reset(self._h, _ptr(mask), _ptr(obs), None, self._stream()), "rr_reset", self._lib)
         else:
             self._reset_to_start(mask, obs)
-        if self._bout is not None or self.step_budget_clocks:  # budgeted mode: a NOT_READY row of the next step keeps these observations
-            self._seed_bout()
+        if self._bout is not None:  # budgeted mode: a NOT_READY row of the next step keeps these observations
+            self._seed_bout(mask, obs)
         return obs if self.obs_kind == 0 else self.get_game_state(1)
 
     def starting_positions(self):
@@ -289,7 +307,7 @@ class BatchedRoboRugbyEnv:
         if a.shape[1] > self.preset.nr:  # RR_EnvBase.py:621-622
             raise Exception(f"{a.shape[1]} commands but only {self.preset.nr} robots.")
         a = a.to(torch.int32).contiguous()
-        own = out is None and bool(self.step_budget_clocks)
+        own = out is None and (bool(self.step_budget_clocks) or self._bout is not None)  # (budget 0 after a budget: parks may remain)
         if own:
             if self._bout is None:  # rows of parked arenas are not written: they must find their previous observation here
                 self._seed_bout()
@@ -312,10 +330,12 @@ class BatchedRoboRugbyEnv:
         return obs, rew, done.view(torch.bool), DebugInfo(obs_g, rew_g, status)
 
     def set_step_budget(self, clocks):
-        """rr_set_step_budget: switch the budgeted step on (clocks > 0) or off (0: parked arenas finish in the next calls)."""
+        """rr_set_step_budget: switch the budgeted step on (clocks > 0) or off (0: parked arenas finish in the next calls), or change
+        the budget.  Arenas parked at the time go on with their step; the NOT_READY rows of step() keep their previous observation
+        (once a handle has had a budget, step() without `out` hands out the persistent buffers whatever the budget)."""
         _lib.check(self._lib.rr_set_step_budget(self._h, int(clocks)), "rr_set_step_budget", self._lib)
         self.step_budget_clocks = int(clocks)
-        if self.step_budget_clocks:
+        if self.step_budget_clocks and self._bout is None:
             self._seed_bout()
 
     def rollout(self, actions, repeat=None, out=None):

@@ -12,56 +12,8 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-NOT_READY = 16384
 
-
-def _chase(obs, cursor, table):
-    """turn toward the ball, else forward; the noise of an arena's k-th accepted step comes from table[k, arena]: the action is a
-    function of the arena's own observation and of how many steps it has accepted -- the same in both modes."""
-    n = obs.shape[0]
-    d = (obs[:, 1] - obs[:, 0] + 540.0) % 360.0 - 180.0
-    a = torch.where(d.abs() < 8, 0, torch.where(d > 0, 2, 3)).to(torch.int32)
-    row = table[cursor.clamp(max=table.shape[0] - 1), torch.arange(n, device=obs.device)]  # [n, na]: >= 8 keeps the chase action
-    a1 = torch.where(row[:, 0] < 8, row[:, 0], a)
-    return torch.cat([a1.view(n, 1), row[:, 1:] % 8], 1).contiguous()
-
-
-def _streams(env, table, steps, budget_mode, max_calls):
-    """runs until every arena has accepted `steps` steps; returns per-arena streams [steps, n, ...] of obs / reward / done / status"""
-    n, dev = env.num_envs, env.device
-    na = table.shape[2]
-    rec_o = torch.zeros(steps, n, 11, device=dev); rec_r = torch.zeros(steps, n, device=dev)
-    rec_d = torch.zeros(steps, n, dtype=torch.uint8, device=dev); rec_s = torch.zeros(steps, n, dtype=torch.int32, device=dev)
-    rec_og = torch.zeros(steps, n, 11, device=dev) if env.has_grumpy else None
-    out = (torch.zeros(n, 11, device=dev), torch.zeros(n, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev),
-           torch.zeros(n, 11, device=dev) if env.has_grumpy else None, torch.zeros(n, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
-    out[0].copy_(env.get_game_state(1))
-    cursor = torch.zeros(n, dtype=torch.long, device=dev)   # steps accepted AND completed
-    parked = torch.zeros(n, dtype=torch.bool, device=dev)
-    ar = torch.arange(n, device=dev)
-    calls = not_ready_rows = 0
-    while int(cursor.min()) < steps:
-        a = _chase(out[0], cursor, table)
-        if budget_mode:  # a parked arena must ignore what it is given: hand it something else
-            a = torch.where(parked.view(n, 1), (a + 3) % 8, a)
-        env.step(a[:, :na], out=out)
-        calls += 1
-        assert calls <= max_calls, "arenas do not make progress"
-        ready = (out[5] & NOT_READY) == 0
-        assert budget_mode or bool(ready.all())
-        not_ready_rows += int((~ready).sum())
-        idx = ar[ready & (cursor < steps)]
-        c = cursor[idx]
-        rec_o[c, idx] = out[0][idx]; rec_r[c, idx] = out[1][idx]; rec_d[c, idx] = out[2][idx]; rec_s[c, idx] = out[5][idx]
-        if rec_og is not None:
-            rec_og[c, idx] = out[3][idx]
-        cursor += ready.long()
-        parked = ~ready
-    return (rec_o, rec_r, rec_d, rec_s, rec_og), calls, not_ready_rows
-
-
-def _equal(a, b):
-    return all(x is None or torch.equal(torch.nan_to_num(x.float(), nan=-7.0), torch.nan_to_num(y.float(), nan=-7.0)) for x, y in zip(a, b))
+from budget_driver import NOT_READY, equal as _equal, streams as _streams  # noqa: E402
 
 
 @pytest.mark.parametrize("preset", ["T", "G"])

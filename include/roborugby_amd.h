@@ -199,6 +199,25 @@ int rr_observe_kind(rr_env *env, int32_t kind, int32_t team, int32_t robot_idx, 
 int rr_observe_kind_f64(rr_env *env, int32_t kind, int32_t team, int32_t robot_idx, int32_t ball_idx, double *obs,
                         int32_t out_dim, void *stream);
 
+/* The hive-mind player's view -- Stephen.__ponder + the observation Stephen.__consult asks for (DQN_pytorch_player.py:38-71) -- for
+ * every arena in ONE launch: which ball each hive robot goes for, and get_game_state(obj_robot = that robot, obj_ball = that ball).
+ * robot_mask: bit r set = robot r (happy robots first) belongs to the hive; robots of both teams may be in it and then compete for
+ *             balls in the same greedy pass, as the reference's class-level hive does.  Empty, or a bit >= NR: -1.
+ * kind:       0 SingleBall_6wayLidar_v2 | 1 SingleBall_6wayLidar (the one Stephen insists on); others: -1.
+ * assign [N,NR] i32: ball index (positive balls first) given to robot r, -1 = none (also for robots outside the hive).
+ * obs [N,NR,11]:     what rr_observe_kind(kind, team of r, r, assign) returns, including the flip for a negative ball / grumpy
+ *                    robot; rows with assign -1 are 0.
+ * Assignment: candidate balls are those whose centre is in neither goal triangle (Goal.ball_in_goal, RR_Goal.py:71) and, with the
+ * opt-in goal scoring, still in play; the (robot, ball) pairs are walked by ascending MyUtils.distance of the two centres, a pair is
+ * taken when neither its robot nor its ball is taken yet.  Distances are compared in the handle's arithmetic type (fp32 for
+ * RR_DTYPE_F32, else fp64).  TIES: the reference does not define the order of exactly equal distances (it iterates a Python set of
+ * players); here the pair with the lower ball index goes first, then the one with the lower robot index.
+ * Read-only on the records: callable between any two steps and changes no later step.  On a handle with a step budget the record
+ * of a parked arena (RR_STATUS_NOT_READY) is in the middle of its step: its row is a sub-step view; the step ignores the action
+ * given to such an arena anyway.  rr_hive_observe_f64 refuses RR_DTYPE_F32 like rr_observe_f64. */
+int rr_hive_observe(rr_env *env, uint32_t robot_mask, int32_t kind, int32_t *assign, float *obs, void *stream);
+int rr_hive_observe_f64(rr_env *env, uint32_t robot_mask, int32_t kind, int32_t *assign, double *obs, void *stream);
+
 /* on != 0: every rr_step / rr_step_thrust first snapshots what the sprites' on_step_begin copies (rectDblPriorStep,
  * RR_Robot.py:116-117, RR_Ball.py:60-61) so that observer kind 4 can report it; the call itself (and rr_reset) seeds the
  * copies from the current poses (the reference holds the stale pre-placement pose until the first step).

@@ -22,6 +22,7 @@
 #include "../../include/roborugby_amd.h"
 #include "rr_sim.hpp"
 #include "rr_extras.hpp"
+#include "rr_hive.hpp"
 #include "rr_kstep.hpp"
 
 using namespace rr;
@@ -312,6 +313,26 @@ __global__ void k_observe_kind(SimParams<typename C::Real> sp, const typename C:
     O tmp[6 * C::NR + 4 * C::NB > 11 ? 6 * C::NR + 4 * C::NB : 11];
     const int m = observe_kind<C, O>(q, sp, kind, team, ridx, bidx, tmp, xs ? xs + (size_t)a * xs_stride<C>() : nullptr);
     for (int k = 0; k < dim; k++) obs[(size_t)a * dim + k] = k < m ? tmp[k] : (O)NAN;
+}
+
+// The hive-mind player's view (rr_hive.hpp): one virtual wave per arena like k_observe -- the greedy robot <- ball assignment of the
+// arena and the observation of every hive robot with its own ball, in one launch.  Read-only on the records.
+// (launch bounds as k_step's: the registers of as many waves as the LDS slices admit -- left alone, the serial observer of kind 1 takes
+// the whole file and halves the occupancy)
+template <class C, typename O, int KIND>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void k_hive(SimParams<typename C::Real> sp, const typename C::Store *recs,
+                                                              const int32_t *irecs, int n, uint32_t robot_mask, int32_t *assign,
+                                                              O *obs) {
+    __shared__ Arena<C> lds[arenas_per_block<C>()];
+    const int wave = threadIdx.x / C::VW; // virtual wave = arena slot in this workgroup
+    const int arena = blockIdx.x * arenas_per_block<C>() + wave;
+    if (arena >= n || wave >= arenas_per_block<C>()) return;
+    Arena<C> &A = lds[wave];
+    const typename C::Store *rec = recs + (size_t)arena * Arena<C>::P_STRIDE;
+    load_record(A, rec, irecs + (size_t)arena * Arena<C>::I_STRIDE);
+    if (KIND == OBS_V2) derive(A, sp);
+    Rec<C> q = { rec };
+    hive_observe<C, O, KIND>(A, q, sp, robot_mask, assign + (size_t)arena * C::NR, obs + (size_t)arena * C::NR * 11);
 }
 
 // Scripted on-device policy of the contact-rich workload ("turn toward ball_angle, else forward, 10 %
@@ -888,6 +909,42 @@ int rr_observe_f64(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, double *
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+extern "C++" {
+template <typename O>
+static int hive_observe_impl(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, O *obs, void *stream) {
+    if (!e || !assign || !obs) return fail(-1, "rr_hive_observe: null argument");
+    if (kind != OBS_V2 && kind != OBS_V1) return fail(-1, "rr_hive_observe: observer kind must be 0 (SingleBall_6wayLidar_v2) or 1 (SingleBall_6wayLidar)");
+    const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy;
+    if (!robot_mask) return fail(-1, "rr_hive_observe: empty robot mask");
+    if (nr < 32 && (robot_mask >> nr)) return fail(-1, "rr_hive_observe: robot mask has a bit at or above the number of robots");
+    const int n = e->cfg.num_envs;
+    DeviceGuard guard(e->cfg.device);
+    int rc = dispatch(e, [&](auto c) {
+        using CC = decltype(c); using RR = typename CC::Real;
+        if constexpr (std::is_same<O, double>::value && !std::is_same<RR, double>::value) {
+            return fail(-1, "rr_hive_observe_f64: handle was created with RR_DTYPE_F32");
+        } else {
+            if (kind == OBS_V2)
+                hipLaunchKernelGGL((k_hive<CC, O, OBS_V2>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream, params_of<RR>(e),
+                                   (const typename CC::Store *)e->recs, (const int32_t *)e->irecs, n, robot_mask, assign, obs);
+            else
+                hipLaunchKernelGGL((k_hive<CC, O, OBS_V1>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream, params_of<RR>(e),
+                                   (const typename CC::Store *)e->recs, (const int32_t *)e->irecs, n, robot_mask, assign, obs);
+            return 0;
+        }
+    });
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+} // extern "C++"
+int rr_hive_observe(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, float *obs, void *stream) {
+    return hive_observe_impl<float>(e, robot_mask, kind, assign, obs, stream);
+}
+int rr_hive_observe_f64(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, double *obs, void *stream) {
+    return hive_observe_impl<double>(e, robot_mask, kind, assign, obs, stream);
 }
 
 int rr_set_state(rr_env *e, const double *robots, const int32_t *ri, const double *balls, const int32_t *step, void *stream) {

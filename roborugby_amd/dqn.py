@@ -601,6 +601,49 @@ def train(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkp
     return res
 
 
+@torch.no_grad()
+def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, epsilon=0.2, preset="G"):
+    """A checkpoint written by train() plays the full game: the happy team is the hive (players.Hive: the reference's
+    DQN_pytorch_player.Stephen -- one policy, one ball per robot), the grumpy team is OG_Twitchy, the line-up of the reference's
+    main.py without its human.  Returns mean return per team over the steps played (per finished episode when any finished) and
+    env-steps/s (HIP events around the loop: policy + step)."""
+    import roborugby_amd as rr
+    from .players import Hive, og_twitchy
+    env = rr.BatchedRoboRugbyEnv(num_envs, preset=preset, device=device, seed=seed, action_mode="thrust")
+    p = env.preset
+    agent = BatchedDQNAgent(batch_size=64, max_mem_size=64, device=device, seed=seed)
+    agent.load_state_dict(torch.load(checkpoint, map_location=device)["agent"])
+    hive = Hive(env, agent, epsilon=epsilon, seed=seed)
+    gen = torch.Generator(device=env.device)
+    gen.manual_seed(seed + 1)
+    env.reset()
+    thrust = torch.zeros(num_envs, 2 * p.nr, dtype=torch.float32, device=env.device)
+    total_h = torch.zeros(num_envs, dtype=torch.float64, device=env.device)
+    total_g = torch.zeros(num_envs, dtype=torch.float64, device=env.device)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(steps):
+        if p.nr_grumpy:
+            thrust[:, 2 * p.nr_happy:] = og_twitchy(num_envs, p.nr_grumpy, generator=gen, device=env.device)
+        hive.act(out=thrust)
+        _, reward, _, info = env.step_thrust(thrust)
+        total_h += reward
+        total_g += info.dblGrumpyScore
+    t1.record()
+    torch.cuda.synchronize(env.device)
+    secs = t0.elapsed_time(t1) / 1e3
+    lr, lrg, _, cnt = env.episode_stats()
+    done = cnt > 0
+    res = dict(mode="play_hive", preset=preset, num_envs=num_envs, steps=steps, epsilon=epsilon, hive_robots=list(hive.robots),
+               return_happy=float(total_h.mean()), return_grumpy=float(total_g.mean()), episodes_finished=int(cnt.sum()),
+               episode_return_happy=float(lr[done].mean()) if bool(done.any()) else None,
+               episode_return_grumpy=float(lrg[done].mean()) if bool(done.any()) else None,
+               env_steps_per_s=num_envs * steps / secs)
+    hive.close()
+    env.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-envs", type=int, default=65536)
@@ -621,7 +664,12 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="gradient steps after the simulator's step instead of next to it")
     ap.add_argument("--no-fused", action="store_true", help="learn step through PyTorch autograd + torch.optim.Adam instead of rr_dqn_update")
     ap.add_argument("--budget", type=int, default=0, help="step_budget_clocks of the env (the budgeted step; 0 = synchronous)")
+    ap.add_argument("--play-hive", default=None, metavar="CHECKPOINT",
+                    help="no training: the checkpoint's policy plays preset G as the happy team's hive mind against OG_Twitchy (--num-envs, --steps)")
     a = ap.parse_args()
+    if a.play_hive:
+        print(json.dumps(play_hive(a.play_hive, a.num_envs, a.steps, a.device, a.seed)))
+        return
     res = train(a.num_envs, a.steps, a.preset, a.device, a.seed, a.checkpoint, a.resume, learn=not a.no_learn,
                 updates_per_step=a.updates_per_step, batch_size=a.batch_size, eps_dec=a.eps_dec, eval_every=a.eval_every,
                 eval_envs=a.eval_envs, log_every=a.log_every, out=a.out, overlap_learn=not a.no_overlap,

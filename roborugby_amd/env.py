@@ -411,6 +411,27 @@ class BatchedRoboRugbyEnv:
         _lib.check(fn(self._h, kind, team, int(robot_idx), int(ball_idx), _ptr(obs), dim, self._stream()), "rr_observe_kind", self._lib)
         return obs
 
+    def hive_observe(self, robot_mask=None, observer=None, f64=False, out=None):
+        """The hive-mind player's view (DQN_pytorch_player.py: Stephen.__ponder + the observation __consult asks for) of every arena in
+        one launch (rr_hive_observe): -> (assign int32 [N,NR], obs [N,NR,11]).  assign[a, r] is the ball robot r of arena a goes for --
+        greedy, nearest (robot, ball) pair first, balls lying in a goal ignored -- or -1 (no ball left, or r is outside the hive);
+        obs[a, r] = get_game_state(robot_idx=r, ball_idx=assign[a, r]) seen from r's own team, 0 where assign is -1.
+        robot_mask: bit r = robot r belongs to the hive (None: every happy robot); observer: 'SingleBall_6wayLidar_v2' or
+        'SingleBall_6wayLidar' (None: the env's own when it is one of the two, else the former); out: (assign, obs) to reuse."""
+        p, N = self.preset, self.num_envs
+        mask = (1 << p.nr_happy) - 1 if robot_mask is None else int(robot_mask)
+        kind = (self.obs_kind if self.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
+        if out is None:
+            out = (self._new((N, p.nr), torch.int32), self._new((N, p.nr, 11), torch.float64 if f64 else torch.float32))
+        assign, obs = out
+        assert assign.dtype == torch.int32 and assign.is_contiguous() and assign.numel() == N * p.nr
+        assert obs.dtype == (torch.float64 if f64 else torch.float32) and obs.is_contiguous() and obs.numel() >= N * p.nr * 11
+        if mask < 0 or mask > 0xFFFFFFFF:
+            raise ValueError("robot_mask: one bit per robot")
+        fn = self._lib.rr_hive_observe_f64 if f64 else self._lib.rr_hive_observe
+        _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(obs), self._stream()), "rr_hive_observe", self._lib)
+        return assign, obs
+
     def render(self, mode="human", arena=0):
         """The pygame window (RR_EnvBase.py:218-258) is UI and out of scope: 'human' is a no-op so callers' render()
         stays harmless; 'rgb_array' returns a CPU debug picture of ONE arena (arena width + 300-px dashboard strip like

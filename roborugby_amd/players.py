@@ -1,5 +1,6 @@
 """Scripted opponents as on-device batched policies.
 
+`Hive` is the reference's hive-mind player (DQN_pytorch_player.py: Stephen): one trained DQN policy drives every robot of the hive.
 `og_twitchy` is the reference's OG_Twitchy (robo_rugby/gym_env/RR_Players.py:14-30): per robot, 5 % turn left (-1, 1),
 45 % straight (1, 1), 45 % back (-1, -1), 5 % turn right (1, -1) -- as (L, R) thrust pairs for `step_thrust`."""
 import ctypes as C
@@ -33,3 +34,120 @@ def chase(env, obs, step=0, noise=0.1, seed=0, na=None, step_of=None, out=None):
                                         C.c_void_p(out.data_ptr()), na, C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)),
                "rr_policy_chase", env._lib)
     return out
+
+
+# GameEnv_Simple._dct_thrust_from_direction (RR_EnvBase.py:593-602): Direction 0..7 -> (L, R)
+_THRUST_FROM_DIRECTION = ((1.0, 1.0), (-1.0, -1.0), (-1.0, 1.0), (1.0, -1.0), (0.0, 1.0), (1.0, 0.0), (-1.0, 0.0), (0.0, -1.0))
+
+
+class Hive:
+    """The reference's hive mind (DQN_pytorch_player.py:10-85, `Stephen`) for every arena at once: each step every hive robot is given
+    a ball (greedy, nearest pair first, balls lying in a goal ignored), the ONE trained agent is asked for an action on
+    get_game_state(obj_robot=robot, obj_ball=its ball) with epsilon 0.2, and the (L, R) thrust pairs go to `env.step_thrust`; a
+    robot without a ball stands still (0, 0).
+
+    act() is rr_hive_observe -> ONE rr_dqn_act over the N * NR rows (padded to a multiple of 64) -> table lookup, all on the current
+    stream: no host synchronisation, and with `out` given no allocation.  `agent`: a roborugby_amd.dqn.BatchedDQNAgent (its Q_eval
+    acts) or the six parameter tensors (fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc3.weight, fc3.bias; float32, on the env's
+    device).  `robots`: indices of the hive's robots, happy robots first (None: the happy team).  `observer`: what the agent was
+    trained on -- None = the env's own when it is SingleBall_6wayLidar(_v2), else SingleBall_6wayLidar_v2 (what `dqn.train` uses;
+    the reference's Stephen insists on 'SingleBall_6wayLidar').  The epsilon draws are a function of (seed, row, number of act()
+    calls so far); a captured graph replays the draws of the call it captured."""
+
+    def __init__(self, env, agent, robots=None, epsilon=0.2, seed=0, observer=None):
+        from . import _lib
+        from .env import OBSERVERS
+        self.env, self.epsilon, self.seed = env, float(epsilon), int(seed)
+        nr, N = env.preset.nr, env.num_envs
+        self.robots = tuple(range(env.preset.nr_happy)) if robots is None else tuple(sorted({int(r) for r in robots}))
+        if not self.robots or self.robots[0] < 0 or self.robots[-1] >= nr:
+            raise ValueError(f"robots: a non-empty subset of 0..{nr - 1}")
+        self.mask = sum(1 << r for r in self.robots)
+        self.kind = (env.obs_kind if env.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
+        if self.kind not in (0, 1):
+            raise ValueError("observer: 'SingleBall_6wayLidar_v2' or 'SingleBall_6wayLidar'")
+        params = list(agent.Q_eval.parameters()) if hasattr(agent, "Q_eval") else list(agent)
+        shapes = [(256, 11), (256,), (256, 256), (256,), (8, 256), (8,)]
+        if [tuple(p.shape) for p in params] != shapes or any(p.dtype != torch.float32 or p.device != env.device or not p.is_contiguous()
+                                                              for p in params):
+            raise ValueError("agent: the reference's 11-256-256-8 network (six contiguous float32 tensors on the env's device)")
+        self._params = params  # (kept alive; the pointers are read at every act(): in-place updates of a learning agent are seen)
+        self._rrlib = _lib.load()
+        self._own_h = None
+        self._dqn_h = getattr(agent, "_fused_h", None)
+        if not self._dqn_h:
+            h = C.c_void_p()
+            _lib.check_dqn(self._rrlib.rr_dqn_create(env.device.index or 0, C.byref(h)), "rr_dqn_create", self._rrlib)
+            self._dqn_h = self._own_h = h
+        self._agent = agent  # (kept alive: a borrowed rr_dqn handle is the agent's)
+        self.rows = (N * nr + 63) // 64 * 64
+        dev = env.device
+        self._assign = torch.empty(N, nr, dtype=torch.int32, device=dev)
+        self._obs = torch.zeros(self.rows, 11, dtype=torch.float32, device=dev)  # (the padding rows stay 0)
+        self._actions = torch.zeros(self.rows, dtype=torch.int32, device=dev)
+        self._thrust = torch.empty(N * nr, 2, dtype=torch.float32, device=dev)
+        self._has = torch.empty(N, nr, dtype=torch.bool, device=dev)
+        self._table = torch.tensor(_THRUST_FROM_DIRECTION, dtype=torch.float32, device=dev)
+        self.calls = 0
+
+    def close(self):
+        h, self._own_h = self._own_h, None
+        if h:
+            self._rrlib.rr_dqn_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def assign(self):
+        """int32 [N, NR]: the ball every robot was given in the last act() (-1: none / outside the hive)"""
+        return self._assign
+
+    @property
+    def obs(self):
+        """float32 [N, NR, 11]: the observations the agent was asked on in the last act()"""
+        return self._obs[:self.env.num_envs * self.env.preset.nr].view(self.env.num_envs, self.env.preset.nr, 11)
+
+    @property
+    def actions(self):
+        """int32 [N, NR]: the agent's answers of the last act() (meaningful where assign >= 0)"""
+        return self._actions[:self.env.num_envs * self.env.preset.nr].view(self.env.num_envs, self.env.preset.nr)
+
+    @torch.no_grad()
+    def act(self, out=None, status=None):
+        """float32 [N, 2*NR] thrust pairs for env.step_thrust.  Columns of robots outside the hive are left as the caller filled them
+        in `out` (0 in a fresh tensor), so another player -- `og_twitchy` -- can drive them.  status (optional, the last step's
+        info.status): rows of arenas that are NOT_READY (budgeted step, parked mid-step) are left alone; the step ignores them."""
+        from . import _lib
+        env = self.env
+        N, nr = env.num_envs, env.preset.nr
+        if out is None:
+            out = torch.zeros(N, 2 * nr, dtype=torch.float32, device=env.device)
+        assert out.dtype == torch.float32 and out.shape == (N, 2 * nr) and out.is_contiguous()
+        stream = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+        _lib.check(env._lib.rr_hive_observe(env._h, self.mask, self.kind, C.c_void_p(self._assign.data_ptr()),
+                                            C.c_void_p(self._obs.data_ptr()), stream), "rr_hive_observe", env._lib)
+        self.calls += 1
+        ptrs = (C.c_void_p * 6)(*[p.data_ptr() for p in self._params])
+        _lib.check_dqn(self._rrlib.rr_dqn_act(self._dqn_h, C.byref(ptrs), C.c_void_p(self._obs.data_ptr()), self.rows,
+                                              min(max(self.epsilon, 0.0), 1.0), self.seed, self.calls & 0xFFFFFFFF,
+                                              C.c_void_p(self._actions.data_ptr()), None, stream), "rr_dqn_act", self._rrlib)
+        torch.index_select(self._table, 0, self._actions[:N * nr], out=self._thrust)
+        torch.ge(self._assign, 0, out=self._has)
+        thr = self._thrust.view(N, nr, 2)
+        thr.mul_(self._has.unsqueeze(-1))  # a robot without a ball stands still
+        out3 = out.view(N, nr, 2)
+        if status is not None:
+            from .env import STATUS_NOT_READY
+            keep = ((status & STATUS_NOT_READY) != 0).view(N, 1)
+            for r in self.robots:
+                out3[:, r] = torch.where(keep, out3[:, r], thr[:, r])
+        elif len(self.robots) == nr:
+            out.copy_(self._thrust.view(N, 2 * nr))
+        else:
+            for r in self.robots:
+                out3[:, r].copy_(thr[:, r])
+        return out

@@ -1,0 +1,117 @@
+"""ctypes binding of the host-emulated hive-mind kernel (tests/emu/rr_hive_emu.cpp) -- test harness only -- and the numpy
+restatement of the greedy assignment rule the CPU and GPU tests compare with."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import oracle_lib as ol
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SO = os.path.join(HERE, "emu", "librr_hive_emu.so")
+CSRC = os.path.join(ol.REPO, "roborugby_amd", "csrc")
+SRC = [os.path.join(HERE, "emu", "rr_hive_emu.cpp")] + [os.path.join(CSRC, f) for f in ("rr_hive.hpp", "rr_extras.hpp", "rr_sim.hpp")]
+PRESET_ID = {"T": 0, "G": 1, "D": 2, "X": 3}
+# lanes per arena the emulation is built for: the product's widths (csrc/rr_kstep.hpp; X: build.shape_lanes) and 64
+LANES = {"T": (2, 4, 64), "G": (8, 16, 32, 64), "D": (4, 64), "X": (8, 64)}
+
+
+def build():
+    if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(s) for s in SRC):
+        tmp = SO + f".tmp{os.getpid()}"
+        subprocess.check_call(["g++", "-O2", "-fPIC", "-ffp-contract=off", "-std=c++17", "-shared", "-o", tmp, SRC[0]])
+        os.replace(tmp, SO)
+    return SO
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = C.CDLL(build())
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        _lib.hive_emu.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, C.c_uint32, C.c_int, ip, dp]
+    return _lib
+
+
+def hive_observe(preset, robots, balls, mask, kind, vw, f32=False):
+    """robots [n,NR,10], balls [n,NB,8] (canonical layout) -> (assign int32 [n,NR], obs float64 [n,NR,11]) of the kernel source"""
+    cfg = ol.PRESETS[preset]
+    nr, nb = cfg["nr_h"] + cfg["nr_g"], cfg["nb_p"] + cfg["nb_n"]
+    r = np.ascontiguousarray(robots, np.float64).reshape(-1, nr, 10)
+    b = np.ascontiguousarray(balls, np.float64).reshape(-1, nb, 8)
+    n = r.shape[0]
+    assert b.shape[0] == n
+    assign = np.full((n, nr), -7, np.int32)
+    obs = np.full((n, nr, 11), np.nan)
+    rc = lib().hive_emu(PRESET_ID[preset], int(vw), int(f32), cfg["W"], cfg["H"], n, r.ctypes.data_as(C.POINTER(C.c_double)),
+                        b.ctypes.data_as(C.POINTER(C.c_double)), int(mask), int(kind), assign.ctypes.data_as(C.POINTER(C.c_int32)),
+                        obs.ctypes.data_as(C.POINTER(C.c_double)))
+    assert rc == 0, (preset, vw, f32)
+    return assign, obs
+
+
+def in_goal(x, y, W, H):
+    """centre inside the happy or the grumpy goal triangle: RightTriangle.contains_point as the reference evaluates it -- bounding box,
+    then slope from the hypotenuse's origin >= the hypotenuse's slope, with x / 0 = +-inf by the sign of x"""
+    def slope(dy, dx):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(dx != 0, dy / np.where(dx != 0, dx, 1.0), np.where(dy > 0, np.inf, np.where(dy < 0, -np.inf, 0.0)))
+    happy = (W - 240 <= x) & (x <= W) & (H - 240 <= y) & (y <= H) & (slope(y - H, x - (W - 240)) >= slope(-240.0, 240.0))
+    grumpy = (0 <= x) & (x <= 240) & (0 <= y) & (y <= 240) & (slope(y - 0.0, x - 240.0) >= slope(240.0, -240.0))
+    return happy | grumpy
+
+
+def tie_bound(dtype):
+    """relative distance gap below which the order of two pairs is not the reference's to decide: 1e-9, or four epsilon of the arithmetic
+    the distances are compared in where that is coarser (fp32)"""
+    return max(1e-9, 4 * float(np.finfo(dtype).eps))
+
+
+def greedy_assign(rxy, bxy, mask, W, H, dtype=np.float64):
+    """The rule of include/roborugby_amd.h (rr_hive_observe) for ONE arena: rxy [NR,2], bxy [NB,2] -> (assign [NR], near_tie).
+    near_tie: two candidate pairs' distances differ by less than tie_bound relative (the tie order is ours, not the reference's)."""
+    rxy, bxy = np.asarray(rxy, dtype), np.asarray(bxy, dtype)
+    nr, nb = len(rxy), len(bxy)
+    cand = ~in_goal(bxy[:, 0], bxy[:, 1], dtype(W), dtype(H)) & (bxy[:, 0] > -900)
+    pairs = [(np.sqrt((bxy[b, 0] - rxy[r, 0]) ** 2 + (bxy[b, 1] - rxy[r, 1]) ** 2), b, r)
+             for b in range(nb) if cand[b] for r in range(nr) if (mask >> r) & 1]
+    pairs.sort(key=lambda t: t[0])  # stable: ball index, then robot index among equal distances
+    d = np.array([float(t[0]) for t in pairs])
+    near = bool(len(d) > 1 and np.any(np.diff(d) < tie_bound(dtype) * np.maximum(d[1:], 1e-300)))
+    assign = np.full(nr, -1, np.int32)
+    taken = set()
+    for _, b, r in pairs:
+        if b not in taken and assign[r] < 0:
+            taken.add(b)
+            assign[r] = b
+    return assign, near
+
+
+def greedy_assign_batch(rxy, bxy, mask, W, H, dtype=np.float64):
+    """greedy_assign for [n] arenas at once: rxy [n,NR,2], bxy [n,NB,2] -> (assign [n,NR], near_tie [n]).  Walking the stably sorted
+    list is taking, min(NR, NB) times, the closest pair whose robot and ball are still free -- the first one in (ball, robot)
+    order among equals, which is what argmin over the ball-major pair axis returns."""
+    rxy, bxy = np.asarray(rxy, dtype), np.asarray(bxy, dtype)
+    n, nr, nb = rxy.shape[0], rxy.shape[1], bxy.shape[1]
+    cand = ~in_goal(bxy[:, :, 0], bxy[:, :, 1], dtype(W), dtype(H)) & (bxy[:, :, 0] > -900)
+    d = np.sqrt((bxy[:, :, None, 0] - rxy[:, None, :, 0]) ** 2 + (bxy[:, :, None, 1] - rxy[:, None, :, 1]) ** 2).astype(np.float64)
+    hive = ((mask >> np.arange(nr)) & 1).astype(bool)
+    d = np.where(cand[:, :, None] & hive[None, None, :], d, np.inf)          # [n, NB, NR]: ball-major
+    flat = np.sort(d.reshape(n, -1), axis=1)
+    with np.errstate(invalid="ignore"):
+        gap = np.diff(flat, axis=1) < tie_bound(dtype) * np.maximum(flat[:, 1:], 1e-300)
+    near = np.any(gap & np.isfinite(flat[:, 1:]), axis=1)
+    assign = np.full((n, nr), -1, np.int32)
+    rows = np.arange(n)
+    for _ in range(min(nr, nb)):
+        p = np.argmin(d.reshape(n, -1), axis=1)
+        b, r = p // nr, p % nr
+        ok = np.isfinite(d[rows, b, r])
+        assign[rows[ok], r[ok]] = b[ok]
+        d[rows[ok], b[ok], :] = np.inf
+        d[rows[ok], :, r[ok]] = np.inf
+    return assign, near

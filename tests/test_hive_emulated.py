@@ -1,0 +1,140 @@
+"""The hive-mind player's kernel source (roborugby_amd/csrc/rr_hive.hpp) on the CPU: compiled with g++ as lane loops
+(tests/hive_emu_lib.py) at the product's lane widths and at 64, against what the reference's own player did
+(tests/golden/hive_{G,X}.npz, tools/gen_hive_golden.py: DQN_pytorch_player.Stephen with a stub mind) and against a numpy
+restatement of the greedy rule on random layouts.
+
+Bars: the assignment is an integer decision -- exactly equal on every recorded step; observations 1e-9, the bar
+tests/test_gpu_parity.py holds observations to.  The order of exactly tied distances is this project's rule, not the reference's:
+the generator drops a step whose two closest candidate distances differ by less than 1e-9 relative, and the fixture has to stay
+within 0 dropped hand-placed states and 1 % dropped episode steps."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import hive_emu_lib as he
+import oracle_lib as ol
+
+
+def _fixture(golden_dir, preset):
+    d = np.load(os.path.join(golden_dir, f"hive_{preset}.npz"))
+    return d, json.loads(str(d["meta"]))
+
+
+@pytest.mark.parametrize("preset", ["G", "X"])
+def test_fixture_is_within_the_near_tie_condition_and_covers_the_degenerate_layouts(golden_dir, preset):
+    d, meta = _fixture(golden_dir, preset)
+    assert meta["dropped_hand_states"] == 0
+    assert meta["dropped_episode_steps"] <= 0.01 * meta["episode_steps"]
+    assert int(d["hand"].sum()) == meta["hand_states"] == 3 * len(meta["hand_layouts"])
+    nr = d["assign"].shape[1]
+    masks = sorted(int(m) for m in np.unique(d["mask"]))
+    assert (1 << nr) - 1 in masks and len(masks) == 3  # happy team, every robot, one robot
+    hive = (d["mask"][:, None] >> np.arange(nr)[None, :]) & 1
+    assert np.all(d["assign"][hive == 0] == -1)
+    hand = d["hand"] == 1
+    got = (d["assign"] >= 0).sum(axis=1)
+    assert np.any(hand & (got == 0))                                  # every ball in a goal: nobody is given one
+    assert np.any(hand & (got > 0) & (got < hive.sum(axis=1)))        # more hive robots than free balls
+    assert np.any(~hand & (got == hive.sum(axis=1)))
+    cfg = ol.PRESETS[preset]
+    ing = he.in_goal(d["balls"][:, :, 0], d["balls"][:, :, 1], cfg["W"], cfg["H"])
+    assert np.any(hand[:, None] & ing & (d["balls"][:, :, 0] > 400)) and np.any(hand[:, None] & ing & (d["balls"][:, :, 0] < 400))
+    taken = np.zeros_like(ing)
+    for r in range(nr):
+        a = d["assign"][:, r]
+        taken[np.arange(len(a))[a >= 0], a[a >= 0]] = True
+    assert not np.any(taken & ing)                                    # the reference never hands out a ball that lies in a goal
+    assert np.abs(d["obs_v1"] - d["obs_v2"]).max() > 1.0              # two different observers were recorded
+
+
+@pytest.mark.parametrize("preset,vw", [(p, vw) for p in ("G", "X") for vw in he.LANES[p]])
+def test_emulated_kernel_reproduces_the_reference_hive(golden_dir, preset, vw):
+    d, _ = _fixture(golden_dir, preset)
+    for mask in np.unique(d["mask"]):
+        s = d["mask"] == mask
+        for kind, key in ((1, "obs_v1"), (0, "obs_v2")):
+            assign, obs = he.hive_observe(preset, d["robots"][s], d["balls"][s], int(mask), kind, vw)
+            assert np.array_equal(assign, d["assign"][s]), (preset, vw, int(mask), kind)
+            err = float(np.abs(obs - d[key][s]).max())
+            assert err <= 1e-9, (preset, vw, int(mask), kind, err)
+
+
+def _random_layouts(rng, n, nr, nb, W, H):
+    """robots / balls in canonical layout (centres only matter): uniform over the arena, a third of the balls thrown into the goal
+    corners, and every 16th layout degenerate -- all balls in goals, or all but one"""
+    robots = np.zeros((n, nr, 10))
+    balls = np.zeros((n, nb, 8))
+    robots[:, :, 0] = rng.uniform(30, W - 30, (n, nr))
+    robots[:, :, 1] = rng.uniform(30, H - 30, (n, nr))
+    robots[:, :, 6] = rng.uniform(0, 360, (n, nr))
+    balls[:, :, 0] = rng.uniform(8, W - 8, (n, nb))
+    balls[:, :, 1] = rng.uniform(8, H - 8, (n, nb))
+    corner = rng.random((n, nb)) < 1 / 3
+    corner[::16] = True
+    keep_one = np.arange(n) % 32 == 16
+    corner[keep_one, rng.integers(0, nb, keep_one.sum())] = False
+    u, v = rng.uniform(0, 110, (n, nb)), rng.uniform(0, 110, (n, nb))  # u + v < 240: inside a triangle with legs of 240
+    far = rng.random((n, nb)) < .5
+    balls[:, :, 0] = np.where(corner, np.where(far, W - 5 - u, 5 + u), balls[:, :, 0])
+    balls[:, :, 1] = np.where(corner, np.where(far, H - 5 - v, 5 + v), balls[:, :, 1])
+    return robots, balls
+
+
+@pytest.mark.parametrize("preset,vw,mask,n", [("G", 8, 0b0011, 6000), ("G", 8, 0b1111, 3000), ("G", 64, 0b1010, 1000), ("G", 16, 0b0100, 500),
+                                              ("X", 8, 0b111, 1500), ("X", 64, 0b011, 500), ("D", 4, 0b11, 500), ("T", 2, 0b1, 500)])
+def test_assignment_equals_the_numpy_restatement_on_random_layouts(preset, vw, mask, n):
+    cfg = ol.PRESETS[preset]
+    nr, nb = cfg["nr_h"] + cfg["nr_g"], cfg["nb_p"] + cfg["nb_n"]
+    rng = np.random.default_rng(1000 * vw + mask)
+    robots, balls = _random_layouts(rng, n, nr, nb, cfg["W"], cfg["H"])
+    assign, obs = he.hive_observe(preset, robots, balls, mask, 0, vw)
+    batch, batch_near = he.greedy_assign_batch(robots[:, :, :2], balls[:, :, :2], mask, cfg["W"], cfg["H"])
+    assert np.array_equal(batch, assign) and not batch_near.any()  # (the vectorised restatement the GPU tests use says the same)
+    none = degenerate = 0
+    for a in range(n):
+        want, near = he.greedy_assign(robots[a, :, :2], balls[a, :, :2], mask, cfg["W"], cfg["H"])
+        assert not near  # (continuous positions: a near-tie would be a bug of the layout generator)
+        assert np.array_equal(assign[a], want), (a, assign[a], want)
+        none += int(np.all(want < 0))
+        degenerate += int(np.sum(want >= 0) < bin(mask).count("1"))
+    assert np.all(obs[assign < 0] == 0) and np.all(np.isfinite(obs))
+    if nb > 1:
+        assert none > 0  # all balls in goals
+        assert degenerate > none or bin(mask).count("1") == 1  # fewer free balls than hive robots
+
+
+def test_exactly_tied_distances_go_to_the_lower_ball_then_the_lower_robot():
+    cfg = ol.PRESETS["G"]
+    robots = np.zeros((1, 4, 10))
+    balls = np.zeros((1, 8, 8))
+    robots[0, :, :2] = [(400, 400), (400, 500), (300, 300), (500, 300)]
+    # balls 2 and 5 at the same distance (50, exactly) from robot 0; balls 1 and 6 both 30 from robot 1; robots 0 and 1 both 50 from ball 3
+    balls[0, :, :2] = [(700, 100), (400, 530), (450, 400), (400, 450), (100, 700), (350, 400), (430, 500), (120, 650)]
+    for vw in he.LANES["G"]:
+        assign, _ = he.hive_observe("G", robots, balls, 0b0011, 0, vw)
+        # sorted pairs: (30, b1, r1), (30, b6, r1), then the 50s in ball order: (b2, r0), (b3, r0), (b3, r1), (b5, r0)
+        assert assign[0].tolist() == [2, 1, -1, -1], (vw, assign)
+        want, near = he.greedy_assign(robots[0, :, :2], balls[0, :, :2], 0b0011, cfg["W"], cfg["H"])
+        assert near and want.tolist() == [2, 1, -1, -1]
+        want, near = he.greedy_assign_batch(robots[:, :, :2], balls[:, :, :2], 0b0011, cfg["W"], cfg["H"])
+        assert near[0] and want[0].tolist() == [2, 1, -1, -1]
+    robots[0, :2, :2] = [(400, 400), (400, 500)]
+    balls[0, :, :2] = [(700, 100), (100, 700), (120, 650), (400, 450), (700, 130), (130, 700), (650, 120), (120, 620)]
+    for vw in he.LANES["G"]:  # one ball, two robots at exactly 50: the lower robot takes it, the other goes for its next best
+        assign, _ = he.hive_observe("G", robots, balls, 0b0011, 0, vw)
+        assert assign[0, 0] == 3 and assign[0, 1] not in (3, -1), (vw, assign)
+
+
+def test_fp32_arithmetic_compares_fp32_distances():
+    cfg = ol.PRESETS["G"]
+    rng = np.random.default_rng(5)
+    robots, balls = _random_layouts(rng, 400, 4, 8, cfg["W"], cfg["H"])
+    robots, balls = robots.astype(np.float32).astype(np.float64), balls.astype(np.float32).astype(np.float64)
+    for vw in (8, 64):
+        assign, obs = he.hive_observe("G", robots, balls, 0b1111, 0, vw, f32=True)
+        for a in range(len(robots)):
+            want, near = he.greedy_assign(robots[a, :, :2], balls[a, :, :2], 0b1111, cfg["W"], cfg["H"], dtype=np.float32)
+            if not near:
+                assert np.array_equal(assign[a], want), (a, assign[a], want)

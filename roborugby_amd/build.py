@@ -5,6 +5,7 @@ flags) next to the library; a library whose recorded hash differs from the sourc
 (A snapshot copied to another box keeps contents, not necessarily timestamps.)"""
 import hashlib
 import os
+import re
 import shutil
 import subprocess
 
@@ -12,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "rr_kernels.hip")
 SRC_KSTEP = os.path.join(HERE, "csrc", "rr_kstep_inst.hip")  # explicit instantiations of the step kernel, one share per -DRR_PART
 SRC_DQN = os.path.join(HERE, "csrc", "rr_dqn.hip")            # fused DQN update (config 5): its own translation unit
-KSTEP_PARTS = 7                                                # == RR_KSTEP_PARTS in csrc/rr_kstep.hpp
-DEPS = [SRC, SRC_KSTEP, SRC_DQN, os.path.join(HERE, "csrc", "rr_kstep.hpp"), os.path.join(HERE, "csrc", "rr_sim.hpp"),
+HDR_KSTEP = os.path.join(HERE, "csrc", "rr_kstep.hpp")         # ... and the table of built configurations
+DEPS = [SRC, SRC_KSTEP, SRC_DQN, HDR_KSTEP, os.path.join(HERE, "csrc", "rr_sim.hpp"),
         os.path.join(HERE, "csrc", "rr_extras.hpp"), os.path.join(HERE, "csrc", "rr_hive.hpp"),
         os.path.join(os.path.dirname(HERE), "include", "roborugby_amd.h")]
 LIB = os.path.join(HERE, "libroborugby_amd.so")
@@ -21,6 +22,25 @@ LIB = os.path.join(HERE, "libroborugby_amd.so")
 # rounded: agrees with the reference's glibc in 99.8 % of the evaluations instead of 97 %; csrc/rr_sim.hpp) -- opt-in, slower
 LIB_EXACT = os.path.join(HERE, "libroborugby_amd_exact.so")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
+
+
+def header_config_table():
+    """(number of k_step translation units, entity counts of the built shapes) as csrc/rr_kstep.hpp states them: RR_KSTEP_PARTS and
+    the rows X(kind, part, NRH, NRG, NBP, NBN, precision, VW, DEF) of the product library's RR_CFG_TABLE.  KSTEP_PARTS and BUILT_SHAPES
+    must say the same (they are literals because an installed package may come without the sources): build_hip_library refuses to
+    compile otherwise, tests/test_abi_and_host.py checks it."""
+    with open(HDR_KSTEP) as f:
+        text = f.read()
+    parts = int(re.search(r"^#define RR_KSTEP_PARTS (\d+)$", text, re.M).group(1))
+    table = re.search(r"^#else // the product library.*?^#endif", text, re.M | re.S).group(0)
+    rows = [tuple(int(v) for v in m.groups()) for m in re.finditer(r"X\((\d+), (\d+), (\d+), (\d+), (\d+), (\d+), \w+, \d+, [01]\)", table)]
+    if not rows or sorted({r[1] for r in rows}) != list(range(parts)):
+        raise RuntimeError("csrc/rr_kstep.hpp: the configuration table does not use every part 0..RR_KSTEP_PARTS-1")
+    return parts, {r[2:] for r in rows}
+
+
+KSTEP_PARTS = 7
+BUILT_SHAPES = {(1, 0, 1, 0), (2, 2, 4, 4), (1, 1, 1, 1)}  # (nrh, nrg, nbp, nbn) inside libroborugby_amd.so; any other: build_shape_library
 
 
 def find_hipcc():
@@ -61,6 +81,8 @@ def build_hip_library(force=False, verbose=False, jobs=None, exact=False):
         return lib_path
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
+    if header_config_table() != (KSTEP_PARTS, BUILT_SHAPES):
+        raise RuntimeError("roborugby_amd/build.py: KSTEP_PARTS / BUILT_SHAPES differ from the table in csrc/rr_kstep.hpp")
     digest = source_hash()
     hipcc = find_hipcc()
     cflags = [f for f in HIPCC_FLAGS if f != "-shared"] + (["-DRR_EXACT_TRIG=1"] if exact else [])
@@ -93,7 +115,6 @@ def build_hip_library(force=False, verbose=False, jobs=None, exact=False):
 
 # ---- one-shape libraries: entity counts outside the built list (the reference's counts are free integers, RR_Constants.py:30-34)
 SHAPES_DIR = os.path.join(HERE, "shapes")
-BUILT_SHAPES = {(1, 0, 1, 0), (2, 2, 4, 4), (1, 1, 1, 1)}  # inside libroborugby_amd.so (csrc/rr_kstep.hpp: RR_FOR_EACH_CFG)
 
 
 def shape_lanes(nrh, nrg, nbp, nbn):

@@ -13,21 +13,24 @@ namespace rr {
 enum : int { KEEPER_NAUGHTY = 1, KEEPER_CHASE = 2, KEEPER_PUSHPOS = 3, KEEPER_DONTDRIVE = 4, KEEPER_KEEPMOVING = 5,
              KEEPER_BASEDESTRUCTION = 6, KEEPER_PUSHNEG = 7 };
 enum : int { OBS_V2 = 0, OBS_V1 = 1, OBS_BASIC = 2, OBS_ALLCOORDS = 3, OBS_ALLCOORDS_PRIOR = 4 };
-// words of the on_step_begin snapshot per arena: rectDblPriorStep copies of the robots (cx, cy, rot), ball_dist_sum,
+// the on_step_begin snapshot of an arena: rectDblPriorStep copies of the robots (cx, cy, rot at 3 r ..), ball_dist_sum,
 // rectDblPriorStep copies of the balls (cx, cy)
-template <class C> constexpr int xs_stride() { return 3 * C::NR + 1 + 2 * C::NB; }
+template <class C> constexpr int xs_dist_sum() { return 3 * C::NR; }
+template <class C> constexpr int xs_ball(int b) { return xs_dist_sum<C>() + 1 + 2 * b; }
+template <class C> constexpr int xs_stride() { return xs_ball<C>(C::NB); }
 
 struct Program { int32_t n; int32_t id[8]; };
 
-// read-only view of one arena's HBM record (field-major layout of Arena<C>::P)
+// read-only view of one arena's HBM record (RecLayout<C>: the field-major layout of Arena<C>::P)
 template <class C> struct Rec {
     using R = typename C::Real;
+    using L = RecLayout<C>;
     const typename C::Store *p; // (fp32 under the F32State policy: widened on read)
-    RR_HD R rcx(int r) const { return (R)p[0 * C::NR + r]; }
-    RR_HD R rcy(int r) const { return (R)p[1 * C::NR + r]; }
-    RR_HD R rrot(int r) const { return (R)p[6 * C::NR + r]; }
-    RR_HD R bcx(int b) const { return (R)p[10 * C::NR + 0 * C::NB + b]; }
-    RR_HD R bcy(int b) const { return (R)p[10 * C::NR + 1 * C::NB + b]; }
+    RR_HD R rcx(int r) const { return (R)p[L::RCX + r]; }
+    RR_HD R rcy(int r) const { return (R)p[L::RCY + r]; }
+    RR_HD R rrot(int r) const { return (R)p[L::RROT + r]; }
+    RR_HD R bcx(int b) const { return (R)p[L::BCX + b]; }
+    RR_HD R bcy(int b) const { return (R)p[L::BCY + b]; }
 };
 template <class C> RR_HD void rec_corners(const Rec<C> &q, const SimParams<typename C::Real> &sp, int r, V2<typename C::Real> c[4]) {
     using R = typename C::Real;
@@ -59,10 +62,10 @@ template <class C> RR_HD void extras_begin(const Rec<C> &q, typename C::Real *xs
     R s = (R)0;
     V2<R> o = { (R)0, (R)0 };
     for (int b = 0; b < C::NBP; b++) { V2<R> c = { q.bcx(b), q.bcy(b) }; s = s + dist<R>(o, c); }
-    xs[3 * C::NR] = s;
+    xs[xs_dist_sum<C>()] = s;
     for (int b = 0; b < C::NB; b++) { // Ball.on_step_begin (RR_Ball.py:60-61): FloatRect.copy() of a 14 x 14 rect
-        xs[3 * C::NR + 1 + 2 * b] = (R)7 + (q.bcx(b) - (R)7);
-        xs[3 * C::NR + 2 + 2 * b] = (R)7 + (q.bcy(b) - (R)7);
+        xs[xs_ball<C>(b)] = (R)7 + (q.bcx(b) - (R)7);
+        xs[xs_ball<C>(b) + 1] = (R)7 + (q.bcy(b) - (R)7);
     }
 }
 // ---- on_step_end: the keeper program in execution order
@@ -90,7 +93,7 @@ RR_HD void extras_end(const Rec<C> &q, const SimParams<typename C::Real> &sp, co
             R s = (R)0;
             V2<R> o = { (R)0, (R)0 };
             for (int b = 0; b < C::NBP; b++) { V2<R> c = { q.bcx(b), q.bcy(b) }; s = s + dist<R>(o, c); }
-            R delta = s - xs[3 * C::NR];
+            R delta = s - xs[xs_dist_sum<C>()];
             if (pg.id[k] == KEEPER_PUSHPOS) { rh += delta * sp.mult_ball; rg -= delta * sp.mult_ball; }
             else { rh -= delta * sp.mult_ball; rg += delta * sp.mult_ball; }
         } break;
@@ -134,19 +137,25 @@ RR_HD void extras_end(const Rec<C> &q, const SimParams<typename C::Real> &sp, co
 // Per-arena bookkeeping `gs` (int32): [0] steps since reset (Goal.lngFrameCount), [1 + g NB + b] the step at which ball b's
 // current stay in goal g began (-1: not inside), [1 + 2 NB + g] / [3 + 2 NB + g] bit masks of the positive / negative balls
 // goal g has consumed (g = 0 happy, 1 grumpy).
-template <class C> constexpr int gs_stride() { return 1 + 2 * C::NB + 4; }
+template <class C> constexpr int gs_consumed() { return 1 + 2 * C::NB; } // [+ g] positive, [+ 2 + g] negative balls goal g has consumed
+template <class C> constexpr int gs_stride() { return gs_consumed<C>() + 4; }
 template <class C> RR_HD void goal_state_clear(int32_t *gs) {
     gs[0] = 0;
     for (int k = 0; k < 2 * C::NB; k++) gs[1 + k] = -1;
-    for (int k = 0; k < 4; k++) gs[1 + 2 * C::NB + k] = 0;
+    for (int k = 0; k < 4; k++) gs[gs_consumed<C>() + k] = 0;
 }
 RR_HD int popcount8(int32_t m) { int n = 0; for (int k = 0; k < 16; k++) n += (m >> k) & 1; return n; }
+// Goal.get_score (RR_Goal.py:87-88) of goal g (0 happy, 1 grumpy)
+template <class C> RR_HD int32_t goal_score(const int32_t *gs, int g) {
+    return 500 * (popcount8(gs[gs_consumed<C>() + g]) - popcount8(gs[gs_consumed<C>() + 2 + g]));
+}
 // rec / irec: the arena's HBM record (mutable: a consumed ball is parked, the episode bookkeeping follows an early end)
 template <class C, typename O>
 RR_HD void goal_step(typename C::Store *rec, int32_t *irec, const SimParams<typename C::Real> &sp, int32_t *gs, bool base_destruction,
                      O *reward, O *reward_g, uint8_t *done, int32_t *status) {
     using R = typename C::Real;
-    constexpr int NR = C::NR, NB = C::NB, BALLS = 10 * NR, ACC = 10 * NR + 8 * NB, I0 = 3 * NR; // irec: step episode ep_len ep_count last_len fault
+    using L = RecLayout<C>;
+    constexpr int NB = C::NB, ACC = L::ACC, GC = gs_consumed<C>();
     int st = *status;
     if (st & ST_WAS_RESET) { goal_state_clear<C>(gs); return; } // Goal.on_reset (RR_Goal.py:47-52)
     if (st & (ST_STEP_AFTER_DONE | ST_NOT_READY)) return; // (budgeted step: a step still in progress is no frame yet)
@@ -155,28 +164,28 @@ RR_HD void goal_step(typename C::Store *rec, int32_t *irec, const SimParams<type
     int alive = 0, dummy = 0;
     for (int g = 0; g < 2; g++)
         for (int b = 0; b < NB; b++) {
-            const bool in_play = rec[BALLS + b] > (R)-900;
-            V2<R> c = { rec[BALLS + b], rec[BALLS + NB + b] };
+            const bool in_play = rec[L::BCX + b] > (R)-900;
+            V2<R> c = { rec[L::BCX + b], rec[L::BCY + b] };
             const bool in = in_play && goal_contains<R>(g == 0, sp.W, sp.H, c, dummy);
             int since = gs[1 + g * NB + b];
             if (in) {
                 if (since >= 0 && frame - since >= 150) { // consumed
                     const bool pos = b < C::NBP;
-                    gs[1 + 2 * NB + (pos ? 0 : 2) + g] |= 1 << b;
+                    gs[GC + (pos ? 0 : 2) + g] |= 1 << b;
                     delta += ((g == 0) == pos) ? (R)500 : (R)-500;
                     const R x = park_x<R>(b), y = park_y<R>();
-                    rec[BALLS + b] = x; rec[BALLS + NB + b] = y;
-                    rec[BALLS + 2 * NB + b] = x - (R)7; rec[BALLS + 3 * NB + b] = x + (R)7;
-                    rec[BALLS + 4 * NB + b] = y - (R)7; rec[BALLS + 5 * NB + b] = y + (R)7;
-                    rec[BALLS + 6 * NB + b] = (R)0; rec[BALLS + 7 * NB + b] = (R)0;
-                    irec[I0 + 6] = 0; // a ball left the field: whatever island the step ended with is not carried over (Arena::I::fzp)
+                    rec[L::BCX + b] = x; rec[L::BCY + b] = y;
+                    rec[L::BL + b] = x - (R)7; rec[L::BRT + b] = x + (R)7;
+                    rec[L::BT + b] = y - (R)7; rec[L::BB + b] = y + (R)7;
+                    rec[L::BVX + b] = (R)0; rec[L::BVY + b] = (R)0;
+                    irec[L::FZP] = 0; // a ball left the field: whatever island the step ended with is not carried over
                     since = -1;
                 } else if (since < 0) since = frame;
             } else since = -1;
             gs[1 + g * NB + b] = since;
         }
-    for (int b = 0; b < NB; b++) alive += rec[BALLS + b] > (R)-900 ? 1 : 0;
-    const bool dh = popcount8(gs[1 + 2 * NB + 2]) >= 3, dg = popcount8(gs[1 + 2 * NB + 3]) >= 3;
+    for (int b = 0; b < NB; b++) alive += rec[L::BCX + b] > (R)-900 ? 1 : 0;
+    const bool dh = popcount8(gs[GC + 2]) >= 3, dg = popcount8(gs[GC + 3]) >= 3;
     R rh = delta, rg = -delta;
     if (base_destruction && (dh || dg)) { // (the reference pays the HAPPY team in both branches: kept)
         const R P = (R)(500 + 200000) * (R)NB; // POINTS_GOAL_DESTROYED, RR_Constants.py:48
@@ -191,8 +200,8 @@ RR_HD void goal_step(typename C::Store *rec, int32_t *irec, const SimParams<type
     st |= (dh ? ST_GOAL_H_DESTROYED : 0) | (dg ? ST_GOAL_G_DESTROYED : 0) | (alive == 0 ? ST_NO_BALLS : 0);
     if ((dh || dg || alive == 0) && !*done) { // game_is_done (RR_EnvBase.py:555-559): the episode ends here
         *done = 1;
-        irec[I0 + 5] = 1; // over: a later call re-places the arena (auto_reset) or flags STEP_AFTER_DONE
-        irec[I0 + 4] = irec[I0 + 2]; irec[I0 + 3] += 1;
+        irec[L::FAULT] = 1; // over: a later call re-places the arena (auto_reset) or flags STEP_AFTER_DONE
+        irec[L::LAST_LEN] = irec[L::EP_LEN]; irec[L::EP_COUNT] += 1;
         rec[ACC + 2] = rec[ACC + 0]; rec[ACC + 3] = rec[ACC + 1];
     }
     *status = st;
@@ -240,7 +249,7 @@ RR_HD int observe_kind(const Rec<C> &q, const SimParams<typename C::Real> &sp, i
             }
         for (int b = 0; b < C::NB; b++) {
             o[n++] = (O)q.bcx(b); o[n++] = (O)q.bcy(b);
-            o[n++] = (O)xs[3 * C::NR + 1 + 2 * b]; o[n++] = (O)xs[3 * C::NR + 2 + 2 * b];
+            o[n++] = (O)xs[xs_ball<C>(b)]; o[n++] = (O)xs[xs_ball<C>(b) + 1];
         }
         return n;
     }

@@ -138,19 +138,20 @@ __global__ void k_set_state(typename C::Store *recs, int32_t *irecs, int n, cons
     if (a >= n) return;
     typename C::Store *rec = recs + (size_t)a * Arena<C>::P_STRIDE;
     int32_t *irec = irecs + (size_t)a * Arena<C>::I_STRIDE;
+    using L = RecLayout<C>;
     constexpr int NR = C::NR, NB = C::NB;
     for (int r = 0; r < NR; r++) {
-        for (int f = 0; f < 10; f++) rec[f * NR + r] = (typename C::Store)robots[((size_t)a * NR + r) * 10 + f];
-        for (int f = 0; f < 3; f++) irec[f * NR + r] = ri[((size_t)a * NR + r) * 3 + f];
+        for (int f = 0; f < L::ROBOT_FIELDS; f++) rec[L::robot_field(f) + r] = (typename C::Store)robots[((size_t)a * NR + r) * L::ROBOT_FIELDS + f];
+        for (int f = 0; f < 3; f++) irec[L::robot_int(f) + r] = ri[((size_t)a * NR + r) * 3 + f];
     }
     for (int b = 0; b < NB; b++)
-        for (int f = 0; f < 8; f++) rec[10 * NR + f * NB + b] = (typename C::Store)balls[((size_t)a * NB + b) * 8 + f];
-    irec[3 * NR + 0] = step[a];
-    irec[3 * NR + 5] = 0; // fault flag
-    irec[3 * NR + 6] = 0; // no island carried over from the previous step (Arena::I::fzp)
+        for (int f = 0; f < L::BALL_FIELDS; f++) rec[L::ball_field(f) + b] = (typename C::Store)balls[((size_t)a * NB + b) * L::BALL_FIELDS + f];
+    irec[L::STEP] = step[a];
+    irec[L::FAULT] = 0;
+    irec[L::FZP] = 0; // no island carried over from the previous step
 #if RR_CARRY
     // the scratch rect where a sub-step leaves it, on the last ball (rr_set_scratch_rect overrides: a dumped reference state has its own)
-    rec[10 * NR + 8 * NB + 4] = rec[10 * NR + 0 * NB + NB - 1]; rec[10 * NR + 8 * NB + 5] = rec[10 * NR + 1 * NB + NB - 1];
+    rec[L::IC] = rec[L::BCX + NB - 1]; rec[L::IC + 1] = rec[L::BCY + NB - 1];
 #endif
 }
 // centre of the reference's scratch rect (Arena::P::ic, parity build only): xy [N,2]
@@ -159,7 +160,7 @@ __global__ void k_scratch_rect(typename C::Store *recs, int n, double *xy, int s
     int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n) return;
 #if RR_CARRY
-    typename C::Store *rec = recs + (size_t)a * Arena<C>::P_STRIDE + 10 * C::NR + 8 * C::NB + 4;
+    typename C::Store *rec = recs + (size_t)a * Arena<C>::P_STRIDE + RecLayout<C>::IC;
     for (int k = 0; k < 2; k++) { if (set) rec[k] = (typename C::Store)xy[(size_t)a * 2 + k]; else xy[(size_t)a * 2 + k] = (double)rec[k]; }
 #else
     (void)recs; (void)xy; (void)set;
@@ -172,14 +173,15 @@ __global__ void k_get_state(const typename C::Store *recs, const int32_t *irecs,
     if (a >= n) return;
     const typename C::Store *rec = recs + (size_t)a * Arena<C>::P_STRIDE;
     const int32_t *irec = irecs + (size_t)a * Arena<C>::I_STRIDE;
+    using L = RecLayout<C>;
     constexpr int NR = C::NR, NB = C::NB;
     for (int r = 0; r < NR; r++) {
-        for (int f = 0; f < 10; f++) robots[((size_t)a * NR + r) * 10 + f] = (double)rec[f * NR + r];
-        for (int f = 0; f < 3; f++) ri[((size_t)a * NR + r) * 3 + f] = irec[f * NR + r];
+        for (int f = 0; f < L::ROBOT_FIELDS; f++) robots[((size_t)a * NR + r) * L::ROBOT_FIELDS + f] = (double)rec[L::robot_field(f) + r];
+        for (int f = 0; f < 3; f++) ri[((size_t)a * NR + r) * 3 + f] = irec[L::robot_int(f) + r];
     }
     for (int b = 0; b < NB; b++)
-        for (int f = 0; f < 8; f++) balls[((size_t)a * NB + b) * 8 + f] = (double)rec[10 * NR + f * NB + b];
-    step[a] = irec[3 * NR + 0];
+        for (int f = 0; f < L::BALL_FIELDS; f++) balls[((size_t)a * NB + b) * L::BALL_FIELDS + f] = (double)rec[L::ball_field(f) + b];
+    step[a] = irec[L::STEP];
 }
 // rr_set_poses, and env.reset(bln_randomize_pos=False) = _set_starting_positions (RR_EnvBase.py:131-153,202-216) through
 // rr_reset_to_poses: masked arenas only, first observations out
@@ -223,7 +225,7 @@ __global__ void k_episode_state(typename C::Store *recs, int32_t *irecs, int n, 
     if (a >= n) return;
     typename C::Store *rec = recs + (size_t)a * Arena<C>::P_STRIDE;
     int32_t *irec = irecs + (size_t)a * Arena<C>::I_STRIDE;
-    constexpr int ACC = 10 * C::NR + 8 * C::NB, I0 = 3 * C::NR + 1; // after mc/thl/thr and step
+    constexpr int ACC = RecLayout<C>::ACC, I0 = RecLayout<C>::EPISODE; // episode .. fault
     for (int k = 0; k < 5; k++) { if (set) irec[I0 + k] = ints[(size_t)a * 5 + k]; else ints[(size_t)a * 5 + k] = irec[I0 + k]; }
     for (int k = 0; k < 4; k++) { if (set) rec[ACC + k] = (typename C::Store)acc[(size_t)a * 4 + k]; else acc[(size_t)a * 4 + k] = (double)rec[ACC + k]; }
 }
@@ -234,11 +236,11 @@ __global__ void k_episode_stats(const typename C::Store *recs, const int32_t *ir
     if (a >= n) return;
     const typename C::Store *rec = recs + (size_t)a * Arena<C>::P_STRIDE;
     const int32_t *irec = irecs + (size_t)a * Arena<C>::I_STRIDE;
-    constexpr int ACC = 10 * C::NR + 8 * C::NB;
-    if (lr) lr[a] = (float)rec[ACC + 2];
-    if (lrg) lrg[a] = (float)rec[ACC + 3];
-    if (ll) ll[a] = irec[3 * C::NR + 4];
-    if (cnt) cnt[a] = irec[3 * C::NR + 3];
+    using L = RecLayout<C>;
+    if (lr) lr[a] = (float)rec[L::ACC + 2];
+    if (lrg) lrg[a] = (float)rec[L::ACC + 3];
+    if (ll) ll[a] = irec[L::LAST_LEN];
+    if (cnt) cnt[a] = irec[L::EP_COUNT];
 }
 
 // ---- other mixins (rr_extras.hpp): thread-per-arena side kernels, straight from the HBM records
@@ -247,10 +249,9 @@ __global__ void k_extras_begin(const typename C::Store *recs, int n, typename C:
     int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n || (mask && !mask[a])) return;
     Rec<C> q = { recs + (size_t)a * Arena<C>::P_STRIDE };
-    // budgeted step: an arena parked mid-step (bit 31 of the record's fzp word, step_arena) began its step in an earlier call -- the copies
-    // taken then are the ones its on_step_end will need (a masked reset re-seeds them: rr_reset clears the mark first)
-    const int32_t *irec = reinterpret_cast<const int32_t *>(q.p + Arena<C>::P_REALS);
-    if (!mask && irec[3 * C::NR + 6] < 0) return;
+    // budgeted step: an arena parked mid-step (record_parked) began its step in an earlier call -- the copies taken then are the
+    // ones its on_step_end will need (a masked reset re-seeds them: rr_reset clears the mark first)
+    if (!mask && record_parked<C>(reinterpret_cast<const int32_t *>(q.p + Arena<C>::P_REALS))) return;
     extras_begin<C>(q, xs + (size_t)a * xs_stride<C>());
 }
 // After k_step, when a non-default keeper program and / or prior-step tracking is on: the program's rewards replace the
@@ -271,7 +272,7 @@ __global__ void k_extras_end(SimParams<typename C::Real> sp, typename C::Store *
     R rh, rg;
     extras_end<C, O>(q, sp, xs + (size_t)a * xs_stride<C>(), pg, (uint32_t)st >> 16, reward + a, reward_g ? reward_g + a : nullptr,
                      status + a, rh, rg);
-    constexpr int ACC = 10 * C::NR + 8 * C::NB; // running return happy/grumpy, last finished return happy/grumpy
+    constexpr int ACC = RecLayout<C>::ACC; // running return happy/grumpy, last finished return happy/grumpy
     rec[ACC + 0] += rh; rec[ACC + 1] += rg;
     if (done[a]) { rec[ACC + 2] = rec[ACC + 0]; rec[ACC + 3] = rec[ACC + 1]; }
 }
@@ -284,12 +285,12 @@ __global__ void k_goal(SimParams<typename C::Real> sp, typename C::Store *recs, 
     goal_step<C, O>(recs + (size_t)a * Arena<C>::P_STRIDE, irecs + (size_t)a * Arena<C>::I_STRIDE, sp, gs + (size_t)a * gs_stride<C>(),
                     base_destruction != 0, reward + a, reward_g ? reward_g + a : nullptr, done + a, status + a);
 }
-// budgeted step: is some arena parked mid-step (bit 31 of its record's fzp word, as k_extras_begin reads it)?  Setters only.
+// budgeted step: is some arena parked mid-step (record_parked, as k_extras_begin reads it)?  Setters only.
 template <class C>
 __global__ void k_any_parked(const int32_t *irecs, int n, int32_t *flag) {
     int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n) return;
-    if (irecs[(size_t)a * Arena<C>::I_STRIDE + 3 * C::NR + 6] < 0) *flag = 1;
+    if (record_parked<C>(irecs + (size_t)a * Arena<C>::I_STRIDE)) *flag = 1;
 }
 template <class C>
 __global__ void k_goal_clear(int n, int32_t *gs, const uint8_t *mask) {
@@ -301,8 +302,7 @@ template <class C>
 __global__ void k_goal_scores(int n, const int32_t *gs, int32_t *scores) { // Goal.get_score (RR_Goal.py:87-88) of the happy / grumpy goal
     int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n) return;
-    const int32_t *g = gs + (size_t)a * gs_stride<C>() + 1 + 2 * C::NB;
-    for (int k = 0; k < 2; k++) scores[2 * a + k] = 500 * (popcount8(g[k]) - popcount8(g[2 + k]));
+    for (int k = 0; k < 2; k++) scores[2 * a + k] = goal_score<C>(gs + (size_t)a * gs_stride<C>(), k);
 }
 template <class C, typename O>
 __global__ void k_observe_kind(SimParams<typename C::Real> sp, const typename C::Store *recs, int n, int kind, int team, int ridx,
@@ -400,15 +400,7 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
     } while (0)
 
 template <typename R> static void fill_params(SimParams<R> &sp, const rr_config &c) {
-    const double W = c.arena_w, H = c.arena_h;
-    sp.W = (R)W; sp.H = (R)H;
-    const double mb = 200000.0 / std::pow(W * W + H * H, .5); // RR_Constants.py:44-46
-    sp.mult_ball = (R)mb;
-    sp.mult_robot = (R)(mb / 100);                              // RR_Constants.py:50
-    sp.rob_cdist = (R)std::pow(10.0 * 10.0 + 20.0 * 20.0, .5);  // MyUtils.py:138 for the 20x40 robot rect
-    const double hr = 7 * std::pow(2.0, .5) / 2;                // RR_TrashyPhysics.py:29
-    sp.inner_h = (R)hr;
-    sp.inner_cdist = (R)std::pow(hr * hr + hr * hr, .5);
+    derive_constants(sp, c.arena_w, c.arena_h);
     sp.game_len = c.game_len_steps; sp.game_mode = c.game_mode; sp.time_limit = c.time_limit; sp.auto_reset = c.auto_reset;
     sp.reset_on_fault = c.reset_on_fault;
     sp.acc_external = 0;
@@ -421,9 +413,9 @@ template <> const SimParams<float> &params_of<float>(const rr_env *e) { return e
 
 // calls f(Cfg<...>{}) for the configuration the handle was created with
 template <class F> static int dispatch(const rr_env *e, F &&f) {
-#define X(kind_, a, b, c, d, R_, vw_) \
+#define X(kind_, part_, a, b, c, d, R_, vw_, def_) \
     if (e->kind == kind_ && e->vw == vw_) return f(Cfg<a, b, c, d, R_, vw_>{});
-    RR_FOR_EACH_CFG(X)
+    RR_CFG_TABLE(X)
 #undef X
     return fail(-1, "corrupt handle");
 }
@@ -436,8 +428,45 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
 };
-template <class C> static dim3 arena_grid(int n) { return dim3((unsigned)((n + arenas_per_block<C>() - 1) / arenas_per_block<C>())); }
-static inline dim3 wave_block() { return dim3(64 * WAVES_PER_BLOCK); }
+
+// The handle as configuration C sees it: typed record pointers and the two launch geometries.  The launchers convert every argument
+// to the kernel's parameter type, so a call site passes nullptr, a mutable pointer for a const one or an int32_t for an int as it is.
+template <class C> struct Typed {
+    using Cfg = C;
+    using R = typename C::Real;
+    const rr_env *e;
+    hipStream_t s;
+    int n() const { return e->cfg.num_envs; }
+    typename C::Store *recs() const { return static_cast<typename C::Store *>(e->recs); }
+    int32_t *irecs() const { return e->irecs; }
+    R *xs() const { return static_cast<R *>(e->xs); }
+    const SimParams<R> &sp() const { return params_of<R>(e); }
+    // one thread per arena, 128 per block: the side kernels that work straight on the HBM records
+    template <class... P, class... A> void per_thread(void (*k)(P...), const A &...a) const {
+        hipLaunchKernelGGL(k, dim3((unsigned)((n() + 127) / 128)), dim3(128), 0, s, static_cast<P>(a)...);
+    }
+    // one virtual wave per arena, a wavefront per workgroup: the kernels that hold the arena in LDS
+    template <class... P, class... A> void per_wave(void (*k)(P...), const A &...a) const {
+        hipLaunchKernelGGL(k, dim3((unsigned)((n() + arenas_per_block<C>() - 1) / arenas_per_block<C>())), dim3(64 * WAVES_PER_BLOCK), 0, s,
+                           static_cast<P>(a)...);
+    }
+};
+// Every entry point that launches for the handle's configuration: f(Typed<C>) runs with the handle's device current, and what its
+// launches left behind is reported.  O = double (entry points with fp64 outputs): a handle that does not compute in fp64 is refused
+// with `f64_refusal`, and f is not instantiated for it -- no kernel with double outputs exists for those configurations.
+template <typename O = float, class F>
+static int on_handle(rr_env *e, const char *who, void *stream, F &&f, const char *f64_refusal = nullptr) {
+    if (!e) return fail(-1, std::string(who) + ": null handle");
+    DeviceGuard guard(e->cfg.device);
+    int rc = dispatch(e, [&](auto c) {
+        using C = decltype(c);
+        if constexpr (std::is_same<O, double>::value && !std::is_same<typename C::Real, double>::value) return fail(-1, f64_refusal);
+        else return f(Typed<C>{ e, (hipStream_t)stream });
+    });
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 extern "C" {
 
@@ -449,17 +478,18 @@ int rr_create(const rr_config *cfg, rr_env **out) {
     if (!cfg || !out) return fail(-1, "rr_create: null argument");
     if (cfg->struct_size != (int32_t)sizeof(rr_config)) return fail(-1, "rr_create: rr_config.struct_size mismatch");
     if (cfg->num_envs <= 0) return fail(-1, "rr_create: num_envs must be positive");
-    int shape;
+    int shape = -1; // of the first row of the table with these entity counts
+#define X(kind_, part_, a, b, c, d, R_, vw_, def_) \
+    if (shape < 0 && cfg->nr_happy == a && cfg->nr_grumpy == b && cfg->nb_pos == c && cfg->nb_neg == d) shape = kind_ % RR_NUM_SHAPES;
+    RR_CFG_TABLE(X)
+#undef X
 #if defined(RR_CUSTOM_SHAPE)
-    if (cfg->nr_happy == RR_NRH && cfg->nr_grumpy == RR_NRG && cfg->nb_pos == RR_NBP && cfg->nb_neg == RR_NBN) shape = 0;
-    else return fail(-1, "rr_create: this library was built for one shape only (roborugby_amd.build.build_shape_library) and it is not this one");
+    if (shape < 0) return fail(-1, "rr_create: this library was built for one shape only (roborugby_amd.build.build_shape_library) and it is not this one");
     if (cfg->dtype == RR_DTYPE_F32) return fail(-1, "rr_create: a one-shape library is built for RR_DTYPE_F64 and RR_DTYPE_F32_STATE only");
 #else
-    if (cfg->nr_happy == 1 && cfg->nr_grumpy == 0 && cfg->nb_pos == 1 && cfg->nb_neg == 0) shape = 0;
-    else if (cfg->nr_happy == 2 && cfg->nr_grumpy == 2 && cfg->nb_pos == 4 && cfg->nb_neg == 4) shape = 1;
-    else if (cfg->nr_happy == 1 && cfg->nr_grumpy == 1 && cfg->nb_pos == 1 && cfg->nb_neg == 1) shape = 2;
-    else return fail(-1, "rr_create: unsupported entity counts (built shapes: 1+0 robots/1+0 balls, 2+2 robots/4+4 balls, 1+1 robots/1+1 balls; "
-                         "any other counts: a one-shape library, roborugby_amd.build.build_shape_library / BatchedRoboRugbyEnv does it on demand)");
+    if (shape < 0)
+        return fail(-1, "rr_create: unsupported entity counts (built shapes: 1+0 robots/1+0 balls, 2+2 robots/4+4 balls, 1+1 robots/1+1 balls; "
+                        "any other counts: a one-shape library, roborugby_amd.build.build_shape_library / BatchedRoboRugbyEnv does it on demand)");
 #endif
     if (cfg->dtype != RR_DTYPE_F64 && cfg->dtype != RR_DTYPE_F32 && cfg->dtype != RR_DTYPE_F32_STATE) return fail(-1, "rr_create: bad dtype");
     if (cfg->dtype == RR_DTYPE_F32_STATE && cfg->step_budget_clocks) return fail(-1, "rr_create: no step budget with RR_DTYPE_F32_STATE");
@@ -470,80 +500,65 @@ int rr_create(const rr_config *cfg, rr_env **out) {
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev) return fail(-1, "rr_create: no such HIP device");
     DeviceGuard guard(cfg->device); // the caller's current device is left as found (like every other entry point)
-    rr_env *e = new (std::nothrow) rr_env();
+    rr_env *e = new (std::nothrow) rr_env(); // every pointer null: from here on rr_destroy cleans up whatever a failure leaves behind
     if (!e) return fail(-3, "rr_create: out of host memory");
     e->cfg = *cfg;
     e->kind = shape + RR_NUM_SHAPES * cfg->dtype;
-    e->vw = 0;
     e->prog.n = 3; e->prog.id[0] = KEEPER_NAUGHTY; e->prog.id[1] = KEEPER_CHASE; e->prog.id[2] = KEEPER_PUSHPOS;
-    e->custom_prog = false; e->track_prior = false; e->xs = nullptr; e->status_buf = nullptr; e->gs = nullptr;
-    e->park = nullptr; e->budget = 0; e->flag = nullptr;
     const char *want = getenv("RR_VW");
     const int want_vw = want ? atoi(want) : 0;
-#define X(kind_, a, b, c, d, R_, vw_) \
+#define X(kind_, part_, a, b, c, d, R_, vw_, def_) \
     if (e->kind == kind_ && (e->vw == 0 || want_vw == vw_)) e->vw = vw_;
-    RR_FOR_EACH_CFG(X)
+    RR_CFG_TABLE(X)
 #undef X
     fill_params(e->spd, *cfg);
     fill_params(e->spf, *cfg);
     size_t pstride = 0, preals = 0, snapw = 0, isnapw = 0;
+    int apb = 1;
     const size_t rsz = cfg->dtype == RR_DTYPE_F64 ? 8 : 4; // bytes per STORED real (the record)
     dispatch(e, [&](auto c) {
         using CC = decltype(c);
         pstride = Arena<CC>::P_STRIDE; preals = Arena<CC>::P_REALS; snapw = Arena<CC>::SNAP_WORDS; isnapw = Arena<CC>::ISNAP_WORDS;
+        apb = arenas_per_block<CC>();
         return 0;
     });
+    const int n = cfg->num_envs;
     e->rec_bytes = pstride * rsz;
     e->irec_bytes = 0; // inside the record
-    e->snap = nullptr; e->isnap = nullptr;
-    hipError_t he = hipMalloc(&e->recs, e->rec_bytes * (size_t)cfg->num_envs);
+    hipError_t he = hipMalloc(&e->recs, e->rec_bytes * (size_t)n);
     if (he == hipSuccess && e->spd.memo) { // scratch of the exact shortcuts (RR_NO_MEMO=1: off)
-        he = hipMalloc((void **)&e->snap, 4 * snapw * (size_t)cfg->num_envs);
-        if (he == hipSuccess) he = hipMalloc((void **)&e->isnap, 4 * isnapw * (size_t)cfg->num_envs);
+        he = hipMalloc((void **)&e->snap, 4 * snapw * (size_t)n);
+        if (he == hipSuccess) he = hipMalloc((void **)&e->isnap, 4 * isnapw * (size_t)n);
     }
     if (he != hipSuccess) {
-        if (e->recs) (void)hipFree(e->recs);
-        if (e->snap) (void)hipFree(e->snap);
-        delete e;
+        rr_destroy(e);
         return fail(-3, std::string("rr_create: hipMalloc: ") + hipGetErrorString(he));
     }
     e->irecs = reinterpret_cast<int32_t *>(static_cast<char *>(e->recs) + preals * rsz);
-    const int n = cfg->num_envs;
     // slowest-first dispatch pays once the groups outnumber the wavefronts resident at a time (a few thousand); one
     // workgroup sorts up to 65,536 keys in a few microseconds.  RR_NO_ORDER=1 switches it off (A/B runs).
-    e->order = nullptr; e->cost = nullptr; e->ngroups = 0;
-    {
-        int apb = 1;
-        dispatch(e, [&](auto c) { using CC = decltype(c); apb = arenas_per_block<CC>(); return 0; });
-        const int ng = (n + apb - 1) / apb;
-        const char *no = getenv("RR_NO_ORDER");
-        if (ng > 2048 && ng <= 65536 && !(no && atoi(no))) {
-            if (hipMalloc((void **)&e->order, sizeof(uint32_t) * ng) == hipSuccess && hipMalloc((void **)&e->cost, sizeof(uint32_t) * ng) == hipSuccess) {
-                e->ngroups = ng;
-                hipLaunchKernelGGL(k_iota, dim3((ng + 255) / 256), dim3(256), 0, 0, e->order, ng);
-                (void)hipMemset(e->cost, 0, sizeof(uint32_t) * ng);
-            } else {
-                if (e->order) (void)hipFree(e->order);
-                e->order = nullptr; e->cost = nullptr;
-            }
+    const int ng = (n + apb - 1) / apb;
+    const char *no = getenv("RR_NO_ORDER");
+    if (ng > 2048 && ng <= 65536 && !(no && atoi(no))) {
+        if (hipMalloc((void **)&e->order, sizeof(uint32_t) * ng) == hipSuccess && hipMalloc((void **)&e->cost, sizeof(uint32_t) * ng) == hipSuccess) {
+            e->ngroups = ng;
+            hipLaunchKernelGGL(k_iota, dim3((ng + 255) / 256), dim3(256), 0, 0, e->order, ng);
+            (void)hipMemset(e->cost, 0, sizeof(uint32_t) * ng);
+        } else { // (index order then)
+            if (e->order) (void)hipFree(e->order);
+            e->order = nullptr; e->cost = nullptr;
         }
     }
     // constructor placement (RR_EnvBase.py:111-116): episode 0 of the counter RNG
     dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_reset<CC, float>), arena_grid<CC>(n), wave_block(), 0, 0, params_of<RR>(e), (typename CC::Store *)e->recs,
-                           e->irecs, n, (const uint8_t *)nullptr, 1, (float *)nullptr, (float *)nullptr);
+        Typed<decltype(c)> v = { e, nullptr };
+        v.per_wave(k_reset<decltype(c), float>, v.sp(), v.recs(), v.irecs(), n, nullptr, 1, nullptr, nullptr);
         return 0;
     });
     he = hipGetLastError();
     if (he == hipSuccess) he = hipDeviceSynchronize();
     if (he != hipSuccess) {
-        (void)hipFree(e->recs);
-        if (e->snap) (void)hipFree(e->snap);
-        if (e->isnap) (void)hipFree(e->isnap);
-        if (e->order) (void)hipFree(e->order);
-        if (e->cost) (void)hipFree(e->cost);
-        delete e;
+        rr_destroy(e);
         return fail(-2, std::string("rr_create: init kernel: ") + hipGetErrorString(he));
     }
     if (cfg->step_budget_clocks) {
@@ -556,36 +571,22 @@ int rr_create(const rr_config *cfg, rr_env **out) {
 int rr_destroy(rr_env *e) {
     if (!e) return 0;
     DeviceGuard guard(e->cfg.device);
-    (void)hipFree(e->recs);
-    if (e->snap) (void)hipFree(e->snap);
-    if (e->isnap) (void)hipFree(e->isnap);
-    if (e->xs) (void)hipFree(e->xs);
-    if (e->gs) (void)hipFree(e->gs);
-    if (e->status_buf) (void)hipFree(e->status_buf);
-    if (e->order) (void)hipFree(e->order);
-    if (e->cost) (void)hipFree(e->cost);
-    if (e->park) (void)hipFree(e->park);
-    if (e->flag) (void)hipFree(e->flag);
+    for (void *p : { e->recs, (void *)e->snap, (void *)e->isnap, e->xs, (void *)e->gs, (void *)e->status_buf, (void *)e->order, (void *)e->cost,
+                     (void *)e->park, (void *)e->flag })
+        if (p) (void)hipFree(p);
     delete e;
     return 0;
 }
 
 int rr_reset(rr_env *e, const uint8_t *mask, float *obs, float *obs_g, void *stream) {
-    if (!e) return fail(-1, "rr_reset: null handle");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_reset<CC, float>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream, params_of<RR>(e),
-                           (typename CC::Store *)e->recs, e->irecs, n, mask, 0, obs, obs_g);
+    return on_handle(e, "rr_reset", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        v.per_wave(k_reset<C, float>, v.sp(), v.recs(), v.irecs(), v.n(), mask, 0, obs, obs_g);
         if (e->track_prior && e->xs) // a re-placed arena has no prior step yet: its copies restart from the new poses
-            hipLaunchKernelGGL((k_extras_begin<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, (const typename CC::Store *)e->recs, n, (RR *)e->xs, mask);
-        if (e->gs) hipLaunchKernelGGL((k_goal_clear<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, n, e->gs, mask); // Goal.on_reset
+            v.per_thread(k_extras_begin<C>, v.recs(), v.n(), v.xs(), mask);
+        if (e->gs) v.per_thread(k_goal_clear<C>, v.n(), e->gs, mask); // Goal.on_reset
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 
 static int check_step_args(rr_env *e, const void *act, int32_t na, const void *obs, const void *reward, const void *done) {
@@ -597,59 +598,40 @@ static int check_step_args(rr_env *e, const void *act, int32_t na, const void *o
     return 0;
 }
 
-// one GameEnv.step for every arena; with a non-default keeper program the side kernels bracket the step kernel
+// one GameEnv.step for every arena; with a non-default keeper program the side kernels bracket the step kernel.
+// Launch-only: no allocation, no synchronise, no host copy.
 extern "C++" {
 template <typename O>
 static int step_impl(rr_env *e, const int32_t *actions, const float *thrust, int32_t na, O *obs, O *reward, uint8_t *done,
                      O *obs_g, O *reward_g, int32_t *status, void *stream, int nsteps = 1, int repeat = 0) {
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    hipStream_t s = (hipStream_t)stream;
     if ((e->custom_prog || e->track_prior || e->gs) && !status) status = e->status_buf; // the side kernels need the NaughtyBots / WAS_RESET bits
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        if constexpr (std::is_same<O, double>::value && !std::is_same<RR, double>::value) {
-            return fail(-1, "fp64 outputs need a handle created with RR_DTYPE_F64");
+    return on_handle<O>(e, "rr_step", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        const int n = v.n();
+        const bool extras = e->custom_prog || e->track_prior;
+        auto step = [&](auto kernel, int ns, int rep, uint32_t *park, uint32_t budget) {
+            v.per_wave(kernel, v.sp(), v.recs(), v.irecs(), n, actions, thrust, na, obs, reward, done, obs_g, reward_g, status, e->order, e->cost,
+                       ns, rep, e->snap, e->isnap, park, budget);
+        };
+        if (extras) v.per_thread(k_extras_begin<C>, v.recs(), n, v.xs(), nullptr);
+        if constexpr (C::MIXED) { // fp32 state: the plain single-step kernel only (rr_set_step_budget / rr_rollout refuse the handle)
+            if (nsteps != 1 || e->park) return fail(-1, "RR_DTYPE_F32_STATE: rr_step only (no rr_rollout, no step budget)");
+            step(k_step<C, O, false>, 1, 0, nullptr, 0);
         } else {
-            if (e->custom_prog || e->track_prior)
-                hipLaunchKernelGGL((k_extras_begin<CC>), dim3((n + 127) / 128), dim3(128), 0, s, (const typename CC::Store *)e->recs, n, (RR *)e->xs, (const uint8_t *)nullptr);
-            if constexpr (CC::MIXED) { // fp32 state: the plain single-step kernel only (rr_set_step_budget / rr_rollout refuse the handle)
-                if (nsteps != 1 || e->park) return fail(-1, "RR_DTYPE_F32_STATE: rr_step only (no rr_rollout, no step budget)");
-                hipLaunchKernelGGL((k_step<CC, O, false>), arena_grid<CC>(n), wave_block(), 0, s, params_of<RR>(e), (typename CC::Store *)e->recs, e->irecs, n,
-                                   actions, thrust, (int)na, obs, reward, done, obs_g, reward_g, status, (const uint32_t *)e->order, e->cost,
-                                   1, 0, e->snap, e->isnap);
-            } else
-            if (nsteps == 1 && e->park)
-                hipLaunchKernelGGL((k_step<CC, O, false, true>), arena_grid<CC>(n), wave_block(), 0, s, params_of<RR>(e), (typename CC::Store *)e->recs, e->irecs, n,
-                                   actions, thrust, (int)na, obs, reward, done, obs_g, reward_g, status, (const uint32_t *)e->order, e->cost,
-                                   1, 0, e->snap, e->isnap, e->park, e->budget);
-            else if (nsteps == 1)
-                hipLaunchKernelGGL((k_step<CC, O, false>), arena_grid<CC>(n), wave_block(), 0, s, params_of<RR>(e), (typename CC::Store *)e->recs, e->irecs, n,
-                                   actions, thrust, (int)na, obs, reward, done, obs_g, reward_g, status, (const uint32_t *)e->order, e->cost,
-                                   1, 0, e->snap, e->isnap);
-            else if constexpr (std::is_same<O, float>::value && CC::VW == default_vw<CC>()) // default lane widths only (build time)
-                hipLaunchKernelGGL((k_step<CC, O, true>), arena_grid<CC>(n), wave_block(), 0, s, params_of<RR>(e), (typename CC::Store *)e->recs, e->irecs, n,
-                                   actions, thrust, (int)na, obs, reward, done, obs_g, reward_g, status, (const uint32_t *)e->order, e->cost,
-                                   nsteps, repeat, e->snap, e->isnap);
-            else
-                return fail(-1, "rr_rollout: built for float outputs and the default lane widths (RR_VW unset) only");
-            if (e->order) hipLaunchKernelGGL(k_order, dim3(1), dim3(ORDER_THREADS), 0, s, (const uint32_t *)e->cost, e->order, e->ngroups);
-            if (e->custom_prog || e->track_prior)
-                hipLaunchKernelGGL((k_extras_end<CC, O>), dim3((n + 127) / 128), dim3(128), 0, s, params_of<RR>(e),
-                                   (typename CC::Store *)e->recs, n, (RR *)e->xs, e->prog, e->custom_prog ? 1 : 0, reward, reward_g, status,
-                                   (const uint8_t *)done);
-            if (e->gs) {
-                int bd = 0;
-                for (int k = 0; k < e->prog.n; k++) bd |= e->prog.id[k] == KEEPER_BASEDESTRUCTION;
-                hipLaunchKernelGGL((k_goal<CC, O>), dim3((n + 127) / 128), dim3(128), 0, s, params_of<RR>(e), (typename CC::Store *)e->recs, e->irecs, n,
-                                   e->gs, bd, reward, reward_g, done, status);
-            }
-            return 0;
+            if (nsteps == 1 && e->park) step(k_step<C, O, false, true>, 1, 0, e->park, e->budget);
+            else if (nsteps == 1) step(k_step<C, O, false>, 1, 0, nullptr, 0);
+            else if constexpr (std::is_same<O, float>::value && default_width<C>()) step(k_step<C, O, true>, nsteps, repeat, nullptr, 0); // (build time)
+            else return fail(-1, "rr_rollout: built for float outputs and the default lane widths (RR_VW unset) only");
         }
-    });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
+        if (e->order) hipLaunchKernelGGL(k_order, dim3(1), dim3(ORDER_THREADS), 0, v.s, (const uint32_t *)e->cost, e->order, e->ngroups);
+        if (extras) v.per_thread(k_extras_end<C, O>, v.sp(), v.recs(), n, v.xs(), e->prog, e->custom_prog ? 1 : 0, reward, reward_g, status, done);
+        if (e->gs) {
+            int bd = 0;
+            for (int k = 0; k < e->prog.n; k++) bd |= e->prog.id[k] == KEEPER_BASEDESTRUCTION;
+            v.per_thread(k_goal<C, O>, v.sp(), v.recs(), v.irecs(), n, e->gs, bd, reward, reward_g, done, status);
+        }
+        return 0;
+    }, "fp64 outputs need a handle created with RR_DTYPE_F64");
 }
 } // extern "C++"
 
@@ -683,13 +665,17 @@ int rr_step_thrust_f64(rr_env *e, const float *thrust, int32_t nk, double *obs, 
     return step_impl<double>(e, nullptr, thrust, nk, obs, reward, done, obs_g, reward_g, status, stream);
 }
 
-static int ensure_snapshot_buffer(rr_env *e) { // on_step_begin snapshot of every arena (xs_stride reals each)
+// The buffers the side kernels need are allocated by the setters that switch them on, never inside rr_step.
+static int ensure_snapshot_buffer(rr_env *e) { // on_step_begin snapshot of every arena (xs_stride arithmetic reals each)
     if (e->xs) return 0;
-    const size_t rsz = e->cfg.dtype == RR_DTYPE_F32 ? 4 : 8; // (arithmetic reals)
-    const size_t nr = (size_t)(e->cfg.nr_happy + e->cfg.nr_grumpy), nb = (size_t)(e->cfg.nb_pos + e->cfg.nb_neg);
-    const size_t bytes = rsz * (3 * nr + 1 + 2 * nb) * (size_t)e->cfg.num_envs;
+    size_t bytes = 0;
+    dispatch(e, [&](auto c) { using C = decltype(c); bytes = sizeof(typename C::Real) * xs_stride<C>() * (size_t)e->cfg.num_envs; return 0; });
     HIP_TRY(hipMalloc(&e->xs, bytes));
     HIP_TRY(hipMemset(e->xs, 0, bytes));
+    return 0;
+}
+static int ensure_status_buffer(rr_env *e) { // stands in for the `status` a caller of rr_step does not pass
+    if (!e->status_buf) HIP_TRY(hipMalloc((void **)&e->status_buf, sizeof(int32_t) * (size_t)e->cfg.num_envs));
     return 0;
 }
 
@@ -698,17 +684,14 @@ static int ensure_snapshot_buffer(rr_env *e) { // on_step_begin snapshot of ever
 static int any_parked(rr_env *e, void *stream, bool &parked) {
     parked = false;
     if (!e->park) return 0;
-    const int n = e->cfg.num_envs;
     hipStream_t s = (hipStream_t)stream;
     if (!e->flag) HIP_TRY(hipMalloc((void **)&e->flag, sizeof(int32_t)));
     HIP_TRY(hipMemsetAsync(e->flag, 0, sizeof(int32_t), s));
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c);
-        hipLaunchKernelGGL((k_any_parked<CC>), dim3((n + 127) / 128), dim3(128), 0, s, (const int32_t *)e->irecs, n, e->flag);
-        return 0;
-    });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
+    if (int rc = on_handle(e, "any_parked", stream, [&](auto v) {
+            v.per_thread(k_any_parked<typename decltype(v)::Cfg>, v.irecs(), v.n(), e->flag);
+            return 0;
+        }))
+        return rc;
     int32_t h = 0;
     HIP_TRY(hipMemcpyAsync(&h, e->flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -744,9 +727,9 @@ int rr_set_reward_program(rr_env *e, const int32_t *ids, int32_t n) {
     for (int i = 0; i < n; i++) e->prog.id[i] = ids[i];
     e->custom_prog = custom;
     e->spd.acc_external = e->spf.acc_external = e->custom_prog ? 1 : 0; // k_extras_end keeps the episode returns then
-    if (e->custom_prog) { // allocated here, never inside rr_step (keeps the step launch-only)
+    if (e->custom_prog) {
         if (int rc = ensure_snapshot_buffer(e)) return rc;
-        if (!e->status_buf) HIP_TRY(hipMalloc((void **)&e->status_buf, sizeof(int32_t) * (size_t)e->cfg.num_envs));
+        if (int rc = ensure_status_buffer(e)) return rc;
     }
     return 0;
 }
@@ -777,34 +760,28 @@ int rr_set_goal_scoring(rr_env *e, int32_t on, void *stream) {
         if (e->gs) { HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); (void)hipFree(e->gs); e->gs = nullptr; }
         return 0;
     }
-    const int n = e->cfg.num_envs;
-    if (!e->status_buf) HIP_TRY(hipMalloc((void **)&e->status_buf, sizeof(int32_t) * (size_t)n));
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c);
-        if (!e->gs && hipMalloc((void **)&e->gs, sizeof(int32_t) * (size_t)gs_stride<CC>() * (size_t)n) != hipSuccess) {
+    if (int rc = ensure_status_buffer(e)) return rc;
+    return on_handle(e, "rr_set_goal_scoring", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        if (!e->gs && hipMalloc((void **)&e->gs, sizeof(int32_t) * (size_t)gs_stride<C>() * (size_t)v.n()) != hipSuccess) {
             e->gs = nullptr;
             return fail(-3, "rr_set_goal_scoring: out of device memory");
         }
-        hipLaunchKernelGGL((k_goal_clear<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, n, e->gs, (const uint8_t *)nullptr);
+        v.per_thread(k_goal_clear<C>, v.n(), e->gs, nullptr);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 int rr_goal_scores(rr_env *e, int32_t *scores, void *stream) {
     if (!e || !scores) return fail(-1, "rr_goal_scores: null argument");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    if (!e->gs) { HIP_TRY(hipMemsetAsync(scores, 0, sizeof(int32_t) * 2 * (size_t)n, (hipStream_t)stream)); return 0; } // the live reference: identically 0
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c);
-        hipLaunchKernelGGL((k_goal_scores<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, n, (const int32_t *)e->gs, scores);
+    if (!e->gs) { // the live reference: identically 0
+        DeviceGuard guard(e->cfg.device);
+        HIP_TRY(hipMemsetAsync(scores, 0, sizeof(int32_t) * 2 * (size_t)e->cfg.num_envs, (hipStream_t)stream));
+        return 0;
+    }
+    return on_handle(e, "rr_goal_scores", stream, [&](auto v) {
+        v.per_thread(k_goal_scores<typename decltype(v)::Cfg>, v.n(), e->gs, scores);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 
 int rr_track_prior_step(rr_env *e, int32_t on, void *stream) {
@@ -816,52 +793,60 @@ int rr_track_prior_step(rr_env *e, int32_t on, void *stream) {
     e->track_prior = on != 0;
     if (!e->track_prior) return 0;
     if (int rc = ensure_snapshot_buffer(e)) return rc;
-    if (!e->status_buf) HIP_TRY(hipMalloc((void **)&e->status_buf, sizeof(int32_t) * (size_t)e->cfg.num_envs));
+    if (int rc = ensure_status_buffer(e)) return rc;
     // until the first step the prior-step copies are copies of the current state (the reference's hold the stale
     // pre-placement pose there: Robot.on_reset / Ball.on_reset copy BEFORE _set_random_positions moves the sprites)
-    const int n = e->cfg.num_envs;
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_extras_begin<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, (const typename CC::Store *)e->recs, n, (RR *)e->xs, (const uint8_t *)nullptr);
+    return on_handle(e, "rr_track_prior_step", stream, [&](auto v) {
+        v.per_thread(k_extras_begin<typename decltype(v)::Cfg>, v.recs(), v.n(), v.xs(), nullptr);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 
+static int check_obs_args(rr_env *e, const void *obs, int32_t team, int32_t ridx, int32_t bidx, const char *who) {
+    if (!e || !obs) return fail(-1, std::string(who) + ": null argument");
+    const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy, nb = e->cfg.nb_pos + e->cfg.nb_neg;
+    if ((team != 1 && team != -1) || ridx >= nr || bidx >= nb) return fail(-1, std::string(who) + ": bad team/robot/ball index");
+    return 0;
+}
 extern "C++" {
 template <typename O>
 static int observe_kind_impl(rr_env *e, int32_t kind, int32_t team, int32_t ridx, int32_t bidx, O *obs, int32_t out_dim, void *stream) {
-    if (!e || !obs) return fail(-1, "rr_observe_kind: null argument");
+    if (int rc = check_obs_args(e, obs, team, ridx, bidx, "rr_observe_kind")) return rc;
     const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy, nb = e->cfg.nb_pos + e->cfg.nb_neg;
-    if ((team != 1 && team != -1) || ridx >= nr || bidx >= nb) return fail(-1, "rr_observe_kind: bad team/robot/ball index");
     const int want = kind == OBS_V2 || kind == OBS_V1 ? 11 : kind == OBS_BASIC ? 5 : kind == OBS_ALLCOORDS ? 3 * nr + 2 * nb :
                      kind == OBS_ALLCOORDS_PRIOR ? 6 * nr + 4 * nb : -1;
     if (want < 0) return fail(-1, "rr_observe_kind: unknown observer kind");
     if (out_dim != want) return fail(-1, "rr_observe_kind: out_dim does not match the observer's size");
     if (kind == OBS_ALLCOORDS_PRIOR && !(e->track_prior && e->xs))
         return fail(-1, "rr_observe_kind: AllCoords_WithPrior needs rr_track_prior_step(env, 1) before the step it looks back on");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        if constexpr (std::is_same<O, double>::value && !std::is_same<RR, double>::value) {
-            return fail(-1, "fp64 outputs need a handle created with RR_DTYPE_F64");
-        } else {
-            if (kind == OBS_V2)
-                hipLaunchKernelGGL((k_observe<CC, O>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream, params_of<RR>(e),
-                                   (const typename CC::Store *)e->recs, (const int32_t *)e->irecs, n, (int)team, (int)ridx, (int)bidx, obs);
-            else
-                hipLaunchKernelGGL((k_observe_kind<CC, O>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, params_of<RR>(e),
-                                   (const typename CC::Store *)e->recs, n, (int)kind, (int)team, (int)ridx, (int)bidx, obs, (int)out_dim,
-                                   kind == OBS_ALLCOORDS_PRIOR ? (const RR *)e->xs : (const RR *)nullptr);
-            return 0;
-        }
-    });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return on_handle<O>(e, "rr_observe_kind", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        if (kind == OBS_V2) v.per_wave(k_observe<C, O>, v.sp(), v.recs(), v.irecs(), v.n(), team, ridx, bidx, obs);
+        else v.per_thread(k_observe_kind<C, O>, v.sp(), v.recs(), v.n(), kind, team, ridx, bidx, obs, out_dim,
+                          kind == OBS_ALLCOORDS_PRIOR ? v.xs() : nullptr);
+        return 0;
+    }, "fp64 outputs need a handle created with RR_DTYPE_F64");
+}
+template <typename O>
+static int observe_impl(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, O *obs, void *stream) {
+    if (int rc = check_obs_args(e, obs, team, ridx, bidx, "rr_observe")) return rc;
+    return on_handle<O>(e, "rr_observe", stream, [&](auto v) {
+        v.per_wave(k_observe<typename decltype(v)::Cfg, O>, v.sp(), v.recs(), v.irecs(), v.n(), team, ridx, bidx, obs);
+        return 0;
+    }, "rr_observe_f64: handle was created with RR_DTYPE_F32");
+}
+template <typename O>
+static int hive_observe_impl(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, O *obs, void *stream) {
+    if (!e || !assign || !obs) return fail(-1, "rr_hive_observe: null argument");
+    if (kind != OBS_V2 && kind != OBS_V1) return fail(-1, "rr_hive_observe: observer kind must be 0 (SingleBall_6wayLidar_v2) or 1 (SingleBall_6wayLidar)");
+    const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy;
+    if (!robot_mask) return fail(-1, "rr_hive_observe: empty robot mask");
+    if (nr < 32 && (robot_mask >> nr)) return fail(-1, "rr_hive_observe: robot mask has a bit at or above the number of robots");
+    return on_handle<O>(e, "rr_hive_observe", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        v.per_wave(kind == OBS_V2 ? k_hive<C, O, OBS_V2> : k_hive<C, O, OBS_V1>, v.sp(), v.recs(), v.irecs(), v.n(), robot_mask, assign, obs);
+        return 0;
+    }, "rr_hive_observe_f64: handle was created with RR_DTYPE_F32");
 }
 } // extern "C++"
 int rr_observe_kind(rr_env *e, int32_t kind, int32_t team, int32_t ridx, int32_t bidx, float *obs, int32_t out_dim, void *stream) {
@@ -870,76 +855,8 @@ int rr_observe_kind(rr_env *e, int32_t kind, int32_t team, int32_t ridx, int32_t
 int rr_observe_kind_f64(rr_env *e, int32_t kind, int32_t team, int32_t ridx, int32_t bidx, double *obs, int32_t out_dim, void *stream) {
     return observe_kind_impl<double>(e, kind, team, ridx, bidx, obs, out_dim, stream);
 }
-
-static int check_obs_args(rr_env *e, const void *obs, int32_t team, int32_t ridx, int32_t bidx) {
-    if (!e || !obs) return fail(-1, "rr_observe: null argument");
-    const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy, nb = e->cfg.nb_pos + e->cfg.nb_neg;
-    if ((team != 1 && team != -1) || ridx >= nr || bidx >= nb) return fail(-1, "rr_observe: bad team/robot/ball index");
-    return 0;
-}
-int rr_observe(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, float *obs, void *stream) {
-    if (int rc = check_obs_args(e, obs, team, ridx, bidx)) return rc;
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_observe<CC, float>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream, params_of<RR>(e),
-                           (const typename CC::Store *)e->recs, (const int32_t *)e->irecs, n, (int)team, (int)ridx, (int)bidx, obs);
-        return 0;
-    });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-int rr_observe_f64(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, double *obs, void *stream) {
-    if (int rc = check_obs_args(e, obs, team, ridx, bidx)) return rc;
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        if constexpr (std::is_same<RR, double>::value) {
-            hipLaunchKernelGGL((k_observe<CC, double>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream,
-                               params_of<RR>(e), (const typename CC::Store *)e->recs, (const int32_t *)e->irecs, n, (int)team, (int)ridx,
-                               (int)bidx, obs);
-            return 0;
-        } else {
-            return fail(-1, "rr_observe_f64: handle was created with RR_DTYPE_F32");
-        }
-    });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-extern "C++" {
-template <typename O>
-static int hive_observe_impl(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, O *obs, void *stream) {
-    if (!e || !assign || !obs) return fail(-1, "rr_hive_observe: null argument");
-    if (kind != OBS_V2 && kind != OBS_V1) return fail(-1, "rr_hive_observe: observer kind must be 0 (SingleBall_6wayLidar_v2) or 1 (SingleBall_6wayLidar)");
-    const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy;
-    if (!robot_mask) return fail(-1, "rr_hive_observe: empty robot mask");
-    if (nr < 32 && (robot_mask >> nr)) return fail(-1, "rr_hive_observe: robot mask has a bit at or above the number of robots");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        if constexpr (std::is_same<O, double>::value && !std::is_same<RR, double>::value) {
-            return fail(-1, "rr_hive_observe_f64: handle was created with RR_DTYPE_F32");
-        } else {
-            if (kind == OBS_V2)
-                hipLaunchKernelGGL((k_hive<CC, O, OBS_V2>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream, params_of<RR>(e),
-                                   (const typename CC::Store *)e->recs, (const int32_t *)e->irecs, n, robot_mask, assign, obs);
-            else
-                hipLaunchKernelGGL((k_hive<CC, O, OBS_V1>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream, params_of<RR>(e),
-                                   (const typename CC::Store *)e->recs, (const int32_t *)e->irecs, n, robot_mask, assign, obs);
-            return 0;
-        }
-    });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-} // extern "C++"
+int rr_observe(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, float *obs, void *stream) { return observe_impl<float>(e, team, ridx, bidx, obs, stream); }
+int rr_observe_f64(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, double *obs, void *stream) { return observe_impl<double>(e, team, ridx, bidx, obs, stream); }
 int rr_hive_observe(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, float *obs, void *stream) {
     return hive_observe_impl<float>(e, robot_mask, kind, assign, obs, stream);
 }
@@ -949,47 +866,27 @@ int rr_hive_observe_f64(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *a
 
 int rr_set_state(rr_env *e, const double *robots, const int32_t *ri, const double *balls, const int32_t *step, void *stream) {
     if (!e || !robots || !ri || !balls || !step) return fail(-1, "rr_set_state: null argument");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_set_state<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, (typename CC::Store *)e->recs, e->irecs,
-                           n, robots, ri, balls, step);
+    return on_handle(e, "rr_set_state", stream, [&](auto v) {
+        v.per_thread(k_set_state<typename decltype(v)::Cfg>, v.recs(), v.irecs(), v.n(), robots, ri, balls, step);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 int rr_get_state(rr_env *e, double *robots, int32_t *ri, double *balls, int32_t *step, void *stream) {
     if (!e || !robots || !ri || !balls || !step) return fail(-1, "rr_get_state: null argument");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_get_state<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, (const typename CC::Store *)e->recs,
-                           (const int32_t *)e->irecs, n, robots, ri, balls, step);
+    return on_handle(e, "rr_get_state", stream, [&](auto v) {
+        v.per_thread(k_get_state<typename decltype(v)::Cfg>, v.recs(), v.irecs(), v.n(), robots, ri, balls, step);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 static int set_poses_impl(rr_env *e, const uint8_t *mask, const double *rxyr, const double *bxyv, float *obs, float *obs_g, void *stream) {
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_set_poses<CC, float>), arena_grid<CC>(n), wave_block(), 0, (hipStream_t)stream, params_of<RR>(e),
-                           (typename CC::Store *)e->recs, e->irecs, n, rxyr, bxyv, mask, obs, obs_g);
+    return on_handle(e, "rr_set_poses", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        v.per_wave(k_set_poses<C, float>, v.sp(), v.recs(), v.irecs(), v.n(), rxyr, bxyv, mask, obs, obs_g);
         if (e->track_prior && e->xs) // like rr_reset: a re-placed arena has no prior step yet
-            hipLaunchKernelGGL((k_extras_begin<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, (const typename CC::Store *)e->recs, n, (RR *)e->xs, mask);
-        if (e->gs) hipLaunchKernelGGL((k_goal_clear<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, n, e->gs, mask);
+            v.per_thread(k_extras_begin<C>, v.recs(), v.n(), v.xs(), mask);
+        if (e->gs) v.per_thread(k_goal_clear<C>, v.n(), e->gs, mask);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 int rr_set_poses(rr_env *e, const double *rxyr, const double *bxyv, void *stream) {
     if (!e || !rxyr || !bxyv) return fail(-1, "rr_set_poses: null argument");
@@ -1001,30 +898,18 @@ int rr_reset_to_poses(rr_env *e, const uint8_t *mask, const double *rxyr, const 
 }
 static int episode_state_impl(rr_env *e, int32_t *ints, double *acc, int set, void *stream) {
     if (!e || !ints || !acc) return fail(-1, "rr_get/set_episode_state: null argument");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_episode_state<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, (typename CC::Store *)e->recs, e->irecs, n, ints, acc, set);
+    return on_handle(e, "rr_get/set_episode_state", stream, [&](auto v) {
+        v.per_thread(k_episode_state<typename decltype(v)::Cfg>, v.recs(), v.irecs(), v.n(), ints, acc, set);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 static int scratch_rect_impl(rr_env *e, double *xy, int set, void *stream) {
     if (!e || !xy) return fail(-1, "rr_get/set_scratch_rect: null argument");
     if (!RR_CARRY) return fail(-3, "rr_get/set_scratch_rect: only the parity build (libroborugby_amd_exact.so) carries the scratch rect");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_scratch_rect<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, (typename CC::Store *)e->recs, n, xy, set);
+    return on_handle(e, "rr_get/set_scratch_rect", stream, [&](auto v) {
+        v.per_thread(k_scratch_rect<typename decltype(v)::Cfg>, v.recs(), v.n(), xy, set);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 int rr_get_scratch_rect(rr_env *e, double *xy, void *stream) { return scratch_rect_impl(e, xy, 0, stream); }
 int rr_set_scratch_rect(rr_env *e, const double *xy, void *stream) { return scratch_rect_impl(e, const_cast<double *>(xy), 1, stream); }
@@ -1033,18 +918,10 @@ int rr_set_episode_state(rr_env *e, const int32_t *ints, const double *acc, void
     return episode_state_impl(e, const_cast<int32_t *>(ints), const_cast<double *>(acc), 1, stream);
 }
 int rr_episode_stats(rr_env *e, float *lr, float *lrg, int32_t *ll, int32_t *cnt, void *stream) {
-    if (!e) return fail(-1, "rr_episode_stats: null handle");
-    const int n = e->cfg.num_envs;
-    DeviceGuard guard(e->cfg.device);
-    int rc = dispatch(e, [&](auto c) {
-        using CC = decltype(c); using RR = typename CC::Real;
-        hipLaunchKernelGGL((k_episode_stats<CC>), dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, (const typename CC::Store *)e->recs,
-                           (const int32_t *)e->irecs, n, lr, lrg, ll, cnt);
+    return on_handle(e, "rr_episode_stats", stream, [&](auto v) {
+        v.per_thread(k_episode_stats<typename decltype(v)::Cfg>, v.recs(), v.irecs(), v.n(), lr, lrg, ll, cnt);
         return 0;
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 int rr_policy_chase(rr_env *e, const float *obs, const int32_t *step_of, uint32_t step, float noise, uint64_t seed, int32_t *actions,
                     int32_t na, void *stream) {

@@ -6,7 +6,6 @@
 #error "compile with -DRR_PART=<0..RR_KSTEP_PARTS-1>"
 #endif
 #define RR_NOTHING
-template <int PART> struct rr_part_tag {};
 // (a macro cannot compare its argument with RR_PART, so every row expands to a constexpr-guarded nothing or to its instantiations
 // through a second macro level keyed on the row's own part number)
 #define RR_IF_PART_0(...)
@@ -41,13 +40,6 @@ template <int PART> struct rr_part_tag {};
 #error "RR_PART out of range"
 #endif
 
-#define X(part, a, b, c, d, R_, vw_, def_) \
-    RR_IF_PART_##part(RR_KSTEP_VARIANTS(RR_NOTHING, a, b, c, d, R_, vw_, float, def_) RR_KSTEP_VARIANTS(RR_NOTHING, a, b, c, d, R_, vw_, double, 0))
-RR_FOR_EACH_CFG_F64_PARTS(X)
-#undef X
-#define X(part, a, b, c, d, R_, vw_, def_) RR_IF_PART_##part(RR_KSTEP_VARIANTS(RR_NOTHING, a, b, c, d, R_, vw_, float, def_))
-RR_FOR_EACH_CFG_F32_PARTS(X)
-#undef X
-#define X(part, a, b, c, d, R_, vw_, def_) RR_IF_PART_##part(RR_KSTEP_PLAIN(RR_NOTHING, a, b, c, d, R_, vw_, float) RR_KSTEP_PLAIN(RR_NOTHING, a, b, c, d, R_, vw_, double))
-RR_FOR_EACH_CFG_F32S_PARTS(X)
+#define X(kind_, part_, a, b, c, d, R_, vw_, def_) RR_IF_PART_##part_(RR_KSTEP_INST_##R_(RR_NOTHING, a, b, c, d, vw_, def_))
+RR_CFG_TABLE(X)
 #undef X

@@ -426,6 +426,18 @@ template <typename R> struct SimParams {
     int32_t acc_external;        // a non-default keeper program owns the episode-return accumulators (k_extras_end), not step_arena
     uint64_t seed, arena_offset;
 };
+// W, H and the constants the reference derives from them and from the fixed sprite sizes (host side: the library's fill_params and the
+// emulations' call it).  pow(x, .5) as the reference writes it, not sqrt: the two may differ in the last bit.
+template <typename R> inline void derive_constants(SimParams<R> &sp, double W, double H) {
+    sp.W = (R)W; sp.H = (R)H;
+    const double mb = 200000.0 / ::pow(W * W + H * H, .5); // RR_Constants.py:44-46
+    sp.mult_ball = (R)mb;
+    sp.mult_robot = (R)(mb / 100);                           // RR_Constants.py:50
+    sp.rob_cdist = (R)::pow(10.0 * 10.0 + 20.0 * 20.0, .5);  // MyUtils.py:138 for the 20x40 robot rect
+    const double hr = 7 * ::pow(2.0, .5) / 2;                // RR_TrashyPhysics.py:29
+    sp.inner_h = (R)hr;
+    sp.inner_cdist = (R)::pow(hr * hr + hr * hr, .5);
+}
 
 // corner / side numbering of FloatRect (MyUtils.py:326-336, :209-229)
 enum { TL = 0, TR = 1, BL = 2, BR = 3 };
@@ -521,6 +533,49 @@ constexpr int lds_pad_words(int body_words, int vw, int real_words) {
 template <class C, int PAD> struct ArenaPadded : ArenaBody<C> { uint32_t lds_pad_[PAD]; };
 template <class C> struct ArenaPadded<C, 0> : ArenaBody<C> {};
 template <class C> using Arena = ArenaPadded<C, lds_pad_words((int)(sizeof(ArenaBody<C>) / 4), C::VW, (int)(sizeof(typename C::Real) / 4))>;
+
+// Where each member of ArenaBody<C>::P / ::I sits in an arena's HBM record: index into the record's stored reals (`rec`) resp. into its
+// ints (`irec`).  Taken from the structs themselves, so everything that works straight on the records (the side kernels, Rec<C>,
+// goal_step, the snapshot's word classes) follows a member that is added, moved or #if-guarded.  Entity e of a field: base + e.
+template <class C> struct RecLayout {
+    using P = typename ArenaBody<C>::P;
+    using I = typename ArenaBody<C>::I;
+    static constexpr int NR = C::NR, NB = C::NB;
+#define RR_P_AT(f) ((int)(offsetof(P, f) / sizeof(typename C::Real)))
+#define RR_I_AT(f) ((int)(offsetof(I, f) / 4))
+    // the robot fields and the ball fields in the order of the canonical state (include/roborugby_amd.h: robots [.., 10], balls [.., 8])
+    static constexpr int ROBOT_FIELDS = 10, BALL_FIELDS = 8;
+    static constexpr int RCX = RR_P_AT(rcx), RCY = RR_P_AT(rcy), RL = RR_P_AT(rl), RRT = RR_P_AT(rrt), RT = RR_P_AT(rt), RB = RR_P_AT(rb),
+                         RROT = RR_P_AT(rrot), PX = RR_P_AT(px), PY = RR_P_AT(py), PROT = RR_P_AT(prot);
+    static constexpr int BCX = RR_P_AT(bcx), BCY = RR_P_AT(bcy), BL = RR_P_AT(bl), BRT = RR_P_AT(brt), BT = RR_P_AT(bt), BB = RR_P_AT(bb),
+                         BVX = RR_P_AT(bvx), BVY = RR_P_AT(bvy);
+    static constexpr int ACC = RR_P_AT(acc); // running return happy/grumpy, last finished return happy/grumpy
+#if RR_CARRY
+    static constexpr int IC = RR_P_AT(ic);   // the scratch rect (parity build only)
+#endif
+    static constexpr int MC = RR_I_AT(mc), THL = RR_I_AT(thl), THR = RR_I_AT(thr);
+    static constexpr int STEP = RR_I_AT(step), EPISODE = RR_I_AT(episode), EP_LEN = RR_I_AT(ep_len), EP_COUNT = RR_I_AT(ep_count),
+                         LAST_LEN = RR_I_AT(last_len), FAULT = RR_I_AT(fault), FZP = RR_I_AT(fzp);
+#undef RR_P_AT
+#undef RR_I_AT
+    static constexpr int robot_field(int f) { return RCX + f * NR; } // f-th field of the canonical robot row
+    static constexpr int ball_field(int f) { return BCX + f * NB; }
+    static constexpr int robot_int(int f) { return MC + f * NR; }    // mc, thl, thr
+    // what the canonical converters (k_set_state / k_get_state, k_episode_state) and the snapshot's word classes rely on
+    static_assert(RCX == 0 && RCY == robot_field(1) && RL == robot_field(2) && RRT == robot_field(3) && RT == robot_field(4) &&
+                  RB == robot_field(5) && RROT == robot_field(6) && PX == robot_field(7) && PY == robot_field(8) && PROT == robot_field(9),
+                  "the 10 robot fields are contiguous, in the canonical order");
+    static_assert(BCX == robot_field(ROBOT_FIELDS) && BCY == ball_field(1) && BL == ball_field(2) && BRT == ball_field(3) &&
+                  BT == ball_field(4) && BB == ball_field(5) && BVX == ball_field(6) && BVY == ball_field(7) && ACC == ball_field(BALL_FIELDS),
+                  "the 8 ball fields follow the robots, contiguous and in the canonical order, and acc follows them");
+    static_assert(sizeof(P::acc) == 4 * sizeof(typename C::Real), "acc has 4 reals");
+#if RR_CARRY
+    static_assert(IC == ACC + 4, "the scratch rect sits right behind acc");
+#endif
+    static_assert(MC == 0 && THL == robot_int(1) && THR == robot_int(2) && STEP == robot_int(3), "mc, thl, thr, then step");
+    static_assert(EP_LEN == EPISODE + 1 && EP_COUNT == EPISODE + 2 && LAST_LEN == EPISODE + 3 && FAULT == EPISODE + 4,
+                  "episode .. fault are 5 consecutive ints (k_episode_state)");
+};
 
 #ifdef RR_REL_IN_RECORD
 #define RR_REL(A) (A).p.rel
@@ -3108,6 +3163,7 @@ template <class C>
 RR_HD void snapshot_compare_update(const Arena<C> &A, uint32_t *snap, int32_t *isnap, bool have, uint32_t &chg_r, uint32_t &chg_re,
                                    uint32_t &chg_b, bool &ax_diff) {
     using R = typename C::Real;
+    using L = RecLayout<C>;
     constexpr int WR = (int)(sizeof(R) / 4);
     constexpr int NW = (int)(sizeof(typename Arena<C>::P) / 4);   // the persistent reals ...
     constexpr int NA = 3 * C::NR * WR;                            // ... + ax, ay, arot: the frame-begin poses the next sub-step's ring update reads
@@ -3130,12 +3186,12 @@ RR_HD void snapshot_compare_update(const Arena<C> &A, uint32_t *snap, int32_t *i
             snap[k] = v;
             if (k < NW) {
                 const int idx = k / WR; // index of the real inside P: 10 robot fields x NR, 8 ball fields x NB, acc[4]
-                if (idx < 10 * C::NR) {
+                if (idx < L::BCX) {
                     const int fld = idx / C::NR; // rcx rcy | rl rrt rt rb | rrot px py prot
                     mine |= d ? (1u << (idx % C::NR + ((fld >= 2 && fld <= 5) ? C::NR : 0))) : 0u;
-                } else if (idx < 10 * C::NR + 8 * C::NB) mine |= d ? (1u << (2 * C::NR + (idx - 10 * C::NR) % C::NB)) : 0u;
+                } else if (idx < L::ACC) mine |= d ? (1u << (2 * C::NR + (idx - L::BCX) % C::NB)) : 0u;
 #if RR_CARRY
-                else if (idx >= 10 * C::NR + 8 * C::NB + 4) mine |= d ? (1u << (2 * C::NR + C::NB - 1)) : 0u; // the scratch rect sits on the last ball
+                else if (idx >= L::IC) mine |= d ? (1u << (2 * C::NR + C::NB - 1)) : 0u; // the scratch rect sits on the last ball
 #endif
             } else {
                 axd = axd | d;
@@ -3187,6 +3243,8 @@ RR_HD int32_t float_bits(float f) { int32_t v; __builtin_memcpy(&v, &f, 4); retu
 // GPU at budgets from 1 clock up).  Whatever rewrites an arena from outside (reset, rr_set_state, rr_set_poses) clears the
 // word, and with it the parked step.
 constexpr int32_t FZP_PARKED = (int32_t)0x80000000; // Arena::I::fzp while the arena is parked mid-step
+// the same question asked of an arena's HBM record (irec = its int part): the side kernels and the emulation's step bracket
+template <class C> RR_HD bool record_parked(const int32_t *irec) { return irec[RecLayout<C>::FZP] < 0; } // (bit 31)
 
 template <class C>
 RR_HD void park_save(Arena<C> &A, uint32_t *buf, int f_next, uint32_t prev_moved, uint32_t naughty, int st, const Hit &fz,

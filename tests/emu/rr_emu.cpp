@@ -23,23 +23,17 @@ template <class C> struct Emu {
     Program prog;     // reward keepers in execution order (default = SimpleDuel3)
     bool custom_prog;
     uint32_t snap[Arena<C>::SNAP_WORDS];
-    typename C::Real xs[3 * C::NR + 1 + 2 * C::NB]; // on_step_begin snapshot (always taken here: AllCoords_WithPrior reads it)
+    typename C::Real xs[xs_stride<C>()]; // on_step_begin snapshot (always taken here: AllCoords_WithPrior reads it)
     int32_t isnap[2 * C::NR];
     int goal_scoring;              // opt-in goal scoring (rr_extras.hpp: goal_step)
-    int32_t gs[1 + 2 * C::NB + 4];
+    int32_t gs[gs_stride<C>()];
     uint32_t park[Arena<C>::PARK_WORDS]; // budgeted step: the parked mid-step state (what the GPU keeps in its side buffer)
     uint32_t park_rng;
 };
 
 template <typename R> static void fill_params(SimParams<R> &sp, double W, double H, int game_len, int game_mode,
                                               int time_limit, int auto_reset, uint64_t seed) {
-    sp.W = (R)W; sp.H = (R)H;
-    double mb = 200000.0 / std::pow(W * W + H * H, .5);
-    sp.mult_ball = (R)mb; sp.mult_robot = (R)(mb / 100);
-    sp.rob_cdist = (R)std::pow(10.0 * 10.0 + 20.0 * 20.0, .5);
-    double hr = 7 * std::pow(2.0, .5) / 2;
-    sp.inner_h = (R)hr;
-    sp.inner_cdist = (R)std::pow(hr * hr + hr * hr, .5);
+    derive_constants(sp, W, H);
     sp.game_len = game_len; sp.game_mode = game_mode; sp.time_limit = time_limit; sp.auto_reset = auto_reset & 1;
     sp.reset_on_fault = (auto_reset >> 1) & 1; // bit 1 of the flag word
     sp.seed = seed; sp.arena_offset = 0; sp.memo = 1; sp.acc_external = 0;
@@ -126,7 +120,7 @@ extern "C" {
 void emu_debug_set_substeps(int k) { g_dbg_substeps = k; }
 void emu_set_goal_scoring(Handle *h, int on) { DISPATCH(h, (e->goal_scoring = on, goal_state_clear<CC>(e->gs))); }
 void emu_goal_scores(Handle *h, int32_t *s2) {
-    DISPATCH(h, { const int32_t *g = e->gs + 1 + 2 * CC::NB; for (int k = 0; k < 2; k++) s2[k] = 500 * (popcount8(g[k]) - popcount8(g[2 + k])); });
+    DISPATCH(h, for (int k = 0; k < 2; k++) s2[k] = goal_score<CC>(e->gs, k));
 }
 void emu_debug_trace(int on) { g_dbg_trace = on; }
 void emu_debug_memo(int on) { g_dbg_memo = on; }
@@ -214,7 +208,7 @@ template <class CC> static int emu_step_t(Emu<CC> *e, const int32_t *actions, co
     RR *xs = e->xs;
     Rec<CC> q = { reinterpret_cast<const RR *>(&e->A.p) };
     if (g_dbg_scrub) scrub_scratch(e);
-    const bool was_parked = e->A.i.fzp < 0;
+    const bool was_parked = record_parked<CC>(reinterpret_cast<const int32_t *>(&e->A.i)); // (the LDS image has the record's layout: P, then I)
     if (!was_parked) extras_begin<CC>(q, xs);
     StepOut<double> o = { obs, obs_g, reward, reward_g, done, &status, g_dbg_memo ? e->snap : nullptr, e->isnap, 0, 0, 0 };
     if (park_mod >= 0) {

@@ -11,13 +11,7 @@ using namespace rr;
 
 template <typename R> static void fill_params(SimParams<R> &sp, double W, double H) {
     memset(&sp, 0, sizeof sp);
-    sp.W = (R)W; sp.H = (R)H;
-    double mb = 200000.0 / std::pow(W * W + H * H, .5);
-    sp.mult_ball = (R)mb; sp.mult_robot = (R)(mb / 100);
-    sp.rob_cdist = (R)std::pow(10.0 * 10.0 + 20.0 * 20.0, .5);
-    double hr = 7 * std::pow(2.0, .5) / 2;
-    sp.inner_h = (R)hr;
-    sp.inner_cdist = (R)std::pow(hr * hr + hr * hr, .5);
+    derive_constants(sp, W, H);
     sp.game_len = 1 << 30; sp.game_mode = 1; sp.memo = 1;
 }
 

@@ -32,6 +32,15 @@ def test_library_exports_every_declared_symbol():
     assert lib.rr_abi_version() == 4
 
 
+def test_build_constants_match_the_configuration_table():
+    """build.py's part count and built shapes are literals (a package may ship without sources): they must say what the one table
+    of built configurations in csrc/rr_kstep.hpp says"""
+    from roborugby_amd import build
+    parts, shapes = build.header_config_table()
+    assert parts == build.KSTEP_PARTS
+    assert shapes == build.BUILT_SHAPES and (2, 2, 4, 4) in shapes
+
+
 def test_config_struct_matches_header_layout():
     from roborugby_amd import _lib
     # 2+4 int32, 2 double, 7 int32 (+4 pad), 2 uint64, 2 uint32 with natural alignment = 96 bytes

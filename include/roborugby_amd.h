@@ -62,7 +62,12 @@ typedef struct rr_config {
     int32_t nr_happy, nr_grumpy, nb_pos, nb_neg; /* RR_Constants.py:30-34; shapes inside libroborugby_amd.so: (1,0,1,0), (2,2,4,4), (1,1,1,1);
                                                     any other counts (<= 8 robots, <= 11 balls, <= 32 ball-robot pairs): a one-shape library of the same
                                                     sources and ABI, hipcc -DRR_CUSTOM_SHAPE ... (roborugby_amd/build.py: build_shape_library) */
-    double arena_w, arena_h;                     /* RR_Constants.py:6-7                                */
+    double arena_w, arena_h;                     /* RR_Constants.py:6-7: the two are independent, each in [300, 8192].  Pass INTEGERS, as the
+                                                    reference's are (its reset draws positions with random.randint over them; the kernel
+                                                    truncates).  Pinned to reference vectors: 800 x 800, 600 x 600, and the non-square
+                                                    1000 x 640 and 480 x 720 (tests/golden: traj / reset _Dwide, _Ttall).  A ball beyond the bottom wall
+                                                    is reflected with H - (bottom - W) * 1.1 -- the WIDTH, as RR_TrashyPhysics.py:336 has it:
+                                                    kept on purpose, it only shows when W != H                                          */
     int32_t game_len_steps; /* RR_Constants.py:25                                                      */
     int32_t game_mode;      /* RR_Constants.py:4: only selects the undo-loop fault rule (EnvBase:417-421) */
     int32_t time_limit;     /* 1: done = step_count >= T (what gym's TimeLimit wrapper reports to

@@ -11,7 +11,17 @@ standins.py and writes small .npz fixtures into tests/golden/:
   mix_<preset>.npz    other reward / observer mixins (part "mix")
   thrust_<preset>.npz trajectories through the continuous-thrust entry GameEnv.step (part "thrust")
 
-usage:  python oracle/refgen/gen_golden.py [G|T|all]
+Non-square arenas: the ids Dwide (D's constants and counts at 1000 x 640) and Ttall
+(T's at 480 x 720) patch the reference's two arena-size constants at load time
+(load_reference.ARENA).  They get the parts traj, reset and -- Dwide only -- mix,
+under their base preset's plans; their traj files also carry `walls`
+[episode, step, 4]: how many calls of bounce_ball_off_wall in that step found the
+ball beyond the left / right / top / bottom wall (the reference's own comparisons,
+RR_TrashyPhysics.py:323-335, made on the ball's rect before the call).  They get no
+kat and no thrust part: neither reads the arena size beyond what the trajectories'
+lidar observations cover.
+
+usage:  python oracle/refgen/gen_golden.py [G|T|D|X|Dwide|Ttall|all] [parts...]
 One preset per process (constants are module globals in the reference), so
 `all` re-invokes this script once per preset.
 """
@@ -28,6 +38,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 GOLD = os.environ.get("RR_GOLDEN_OUT") or os.path.join(REPO, "tests", "golden")  # (tests regenerate into a scratch directory)
 sys.path.insert(0, HERE)
+from load_reference import BASE  # noqa: E402  non-square id -> the preset whose plans it runs (importing it reads no reference code)
 
 META = {
     "generator": "oracle/refgen/gen_golden.py",
@@ -116,9 +127,18 @@ class Counters:
         self.c = {k: 0 for k in self.NAMES}
         self.c["undo_naughty"] = 0
         self.c["robot_collision"] = 0
+        self.walls = [0, 0, 0, 0]  # calls of bounce_ball_off_wall that found the ball beyond left / right / top / bottom (run_episode zeroes it per step)
         for name in self.NAMES:
             orig = getattr(R.tp, name)
             setattr(R.tp, name, self._wrap(name, orig))
+        counted, W, H, me = R.tp.bounce_ball_off_wall, R.const.ARENA_WIDTH, R.const.ARENA_HEIGHT, self
+
+        def wall(ball):  # the four comparisons of RR_TrashyPhysics.py:323,327,331,335 on the rect as the call finds it
+            r = ball.rectDbl
+            for i, beyond in enumerate((r.left < 0, r.right > W, r.top <= 0, r.bottom >= H)):
+                me.walls[i] += int(beyond)
+            return counted(ball)
+        R.tp.bounce_ball_off_wall = wall
         cls = R.base.GameEnv
         orig_undo = cls._undo_naughty_movement
         me = self
@@ -185,7 +205,8 @@ def run_episode(R, env, kind, NA, nsteps, rng, scramble, vmax, cnt=None):
              step=np.zeros(nsteps + 1, np.int32))
     out = dict(actions=np.full((nsteps, NR), -1, np.int32), obs=np.full((nsteps, 11), NAN),
                obs_g=np.full((nsteps, 11), NAN), reward=np.zeros(nsteps), reward_g=np.zeros(nsteps),
-               done=np.zeros(nsteps, np.uint8), naughty=np.zeros(nsteps, np.int32), warn=np.zeros(nsteps, np.int32))
+               done=np.zeros(nsteps, np.uint8), naughty=np.zeros(nsteps, np.int32), warn=np.zeros(nsteps, np.int32),
+               walls=np.zeros((nsteps, 4), np.int32))
 
     def put(i):
         d = dump_state(env, R)
@@ -201,6 +222,7 @@ def run_episode(R, env, kind, NA, nsteps, rng, scramble, vmax, cnt=None):
         try:
             if cnt is not None:
                 cnt.warns = 0
+                cnt.walls[:] = [0, 0, 0, 0]
             o, r, d, info = env.step(acts)
         except Exception as e:  # the reference raises from inside step
             exc = exc_code(e)
@@ -217,6 +239,8 @@ def run_episode(R, env, kind, NA, nsteps, rng, scramble, vmax, cnt=None):
                 nm |= 1 << i
         out["naughty"][s] = nm
         out["warn"][s] = cnt.warns if cnt is not None else 0
+        if cnt is not None:
+            out["walls"][s] = cnt.walls
         put(s + 1)
         length = s + 1
         if d:
@@ -241,13 +265,14 @@ def gen_traj(R, preset):
     env = R.envs.SimpleDuel3()
     reset_scratch_rect(R)
     NR = len(env.lstRobots)
-    rng = random.Random({"G": 20201, "T": 20202, "D": 20203, "X": 20204}[preset])
-    if preset in ("D", "X"):  # two robots (one per team), two balls (one of each colour), G's arena and episode length
+    base = BASE.get(preset, preset)  # a non-square id runs its base preset's plan from its base preset's seed
+    rng = random.Random({"G": 20201, "T": 20202, "D": 20203, "X": 20204}[base])
+    if base in ("D", "X"):  # two robots (one per team), two balls (one of each colour), G's arena and episode length
         plan = [("random", NR, 150, False, 0), ("chase", NR, 300, False, 0), ("chase_noisy", NR, 300, True, 6.0),
                 ("chase", NR, 300, True, 9.0), ("forward", NR, 200, True, 3.0), ("chase", 1, 300, True, 5.0),
                 ("chase_noisy", NR, 300, True, 12.0), ("chase", NR, 300, True, 2.0), ("random", NR, 200, True, 10.0),
                 ("chase", NR, 300, False, 0), ("chase_noisy", NR, 300, True, 4.0), ("chase", NR, 300, True, 7.0)]
-    elif preset == "G":
+    elif base == "G":
         plan = [("random", NR, 60, False, 0), ("chase", NR, 220, False, 0), ("chase_noisy", NR, 220, True, 6.0),
                 ("chase", NR, 220, True, 9.0), ("forward", NR, 150, True, 3.0), ("chase", 1, 150, True, 5.0),
                 ("chase", 2, 150, False, 0), ("chase_noisy", NR, 220, True, 12.0), ("chase", NR, 220, True, 2.0),
@@ -269,6 +294,8 @@ def gen_traj(R, preset):
     smax = max(e["actions"].shape[0] for e in eps)
     packed = {}
     for k in eps[0]:
+        if k == "walls" and preset not in BASE:
+            continue  # recorded for the non-square ids only: the square fixtures are as committed
         arrs = [e[k] for e in eps]
         if arrs[0].ndim == 0 or k in ("obs0", "obs0_g"):
             packed[k] = np.stack(arrs)
@@ -281,6 +308,7 @@ def gen_traj(R, preset):
             pad.append(p)
         packed[k] = np.stack(pad)
     meta = dict(META, preset=preset, plan=[list(p) for p in plan], coverage=cnt.c,
+                **(dict(arena=[R.const.ARENA_WIDTH, R.const.ARENA_HEIGHT], walls="left,right,top,bottom") if preset in BASE else {}),
                 state_layout=dict(robots="cx,cy,left,right,top,bottom,rot,prev_x,prev_y,prev_rot (prev = ring entry moveCount-1, NaN if absent)",
                                   robots_i="moveCount,lthrust,rthrust", balls="cx,cy,left,right,top,bottom,vx,vy",
                                   inner="_rectBallInner cx,cy,rot (module-global scratch rect, RR_TrashyPhysics.py:29-36)"))
@@ -599,7 +627,8 @@ def gen_mix(R, preset):
     # The env constructors place sprites with Python's global `random`, and until the first step AllCoords_WithPrior reports the
     # stale pre-placement rectDblPriorStep of that construction (alt0_allp_*, row 0 of each mixin stack): seeded here, so that the
     # part reproduces its file whatever ran before it in the process (row 0 used to depend on the earlier parts).
-    random.seed(90210 + (1 if preset == "G" else 0))
+    shape = BASE.get(preset, preset)
+    random.seed(90210 + (1 if shape == "G" else 0))
     cnt = Counters(R)  # also turns the reference's endless GAME_MODE warning loop into an exception
     R.envs.SimpleDuel3()  # first constructed env fixes the shared class-level observation_space (Obs:30-37)
 
@@ -613,13 +642,13 @@ def gen_mix(R, preset):
     progs = {"A": ["DontDriveInGoals", "KeepMovingGuys", "PushNegBallsFromGoal", "BaseDestruction", "PushPosBallsToGoal",
                    "ChasePosBall"],
              "B": ["KeepMovingGuys", "NaughtyBots", "DontDriveInGoals"]}
-    rng = random.Random(4242 if preset == "G" else 4343)
+    rng = random.Random(4242 if shape == "G" else 4343)
     W, H = c.ARENA_WIDTH, c.ARENA_HEIGHT
     eps = []
     for which, cls in (("A", MixA), ("B", MixB)):
         env = cls()
         NR, NB = len(env.lstRobots), len(env.lstBalls)
-        for e in range(4 if preset == "G" else 5):
+        for e in range(4 if shape == "G" else 5):
             random.seed(rng.randint(0, 1 << 30))
             env.reset()
             # lure the chasers into the goal corners: park the balls inside the goal triangles
@@ -627,7 +656,7 @@ def gen_mix(R, preset):
             for i, b in enumerate(env.lstBalls):
                 if e % 2 == 0:
                     b.rectDbl.center = spots[(i + e) % len(spots)]
-            nsteps = 160 if preset == "G" else 260
+            nsteps = 160 if shape == "G" else 200 if preset == "Dwide" else 260  # (Dwide: shorter than D's, keeps the file under 1 MB)
             S = dict(robots=[], robots_i=[], balls=[], inner=[], step=[])
             rec = {k: [] for k in ("actions", "reward", "reward_g", "done", "v1_h", "v1_g", "basic_h", "basic_g", "all_h", "all_g",
                                    "allp_h", "allp_g", "basic_last", "v1_last_negball")}
@@ -700,11 +729,14 @@ def main():
     if which == "all":
         for p in ("T", "G", "D", "X"):
             subprocess.check_call([sys.executable, os.path.abspath(__file__), p])
+        for p, parts in (("Dwide", ["reset", "traj", "mix"]), ("Ttall", ["reset", "traj"])):
+            subprocess.check_call([sys.executable, os.path.abspath(__file__), p] + parts)
         return
     from load_reference import load_reference
     R = load_reference(which)
     os.makedirs(GOLD, exist_ok=True)
-    parts = sys.argv[2:] or ["kat", "reset", "traj"]
+    parts = sys.argv[2:] or (["reset", "traj"] if which in BASE else ["kat", "reset", "traj"])
+    assert which not in BASE or not {"kat", "thrust"} & set(parts), "the non-square ids have no kat and no thrust part"
     if "kat" in parts:
         gen_kat(R, which)
     if "reset" in parts:

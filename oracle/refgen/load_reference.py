@@ -7,13 +7,19 @@ RR_Constants.py with that one assignment flipped into a module object that is
 registered before anything else imports it.  Preset D (the 1+1 / 1+1 duel) keeps
 GAME_MODE = True and sets the four entity counts of RR_Constants.py:30-34 to 1 the
 same way; preset X sets them to 2 + 1 robots and 2 + 3 balls (a shape outside the
-library's built list: odd counts, unequal teams).  Nothing on disk changes.
+library's built list: odd counts, unequal teams).  The non-square ids of ARENA
+(Dwide: D at 1000 x 640, Ttall: T at 480 x 720) replace the two arena-size
+assignments of RR_Constants.py:6-7 the same way, on top of their base preset's
+patches; the sizes are integers, as the reference's own are (its reset draws them
+through random.randint).  Nothing on disk changes.
 """
 import os
 import sys
 import types
 
 REF_ROOT = os.environ.get("RR_REFERENCE_ROOT", "/root/reference")
+BASE = {"Dwide": "D", "Ttall": "T"}                    # preset whose constants and entity counts the id keeps
+ARENA = {"Dwide": (1000, 640), "Ttall": (480, 720)}    # (ARENA_WIDTH, ARENA_HEIGHT) patched in; every other id keeps the reference's
 
 
 def reference_available():
@@ -21,8 +27,10 @@ def reference_available():
 
 
 def load_reference(preset):
-    """Returns a namespace with the reference modules for preset 'G' or 'T'."""
+    """Returns a namespace with the reference modules for preset 'G', 'T', 'D', 'X' or one of the non-square ids of ARENA."""
+    ident, preset = preset, BASE.get(preset, preset)
     assert preset in ("G", "T", "D", "X")
+    arena = ARENA.get(ident)
     if not reference_available():
         raise RuntimeError("reference tree not present at %s" % REF_ROOT)
     sys.dont_write_bytecode = True
@@ -36,9 +44,10 @@ def load_reference(preset):
     if "robo_rugby.gym_env.RR_Constants" in sys.modules:
         const = sys.modules["robo_rugby.gym_env.RR_Constants"]
         have = {4: "G", 2: "D", 3: "X"}[const.NUM_ROBOTS_TOTAL] if const.GAME_MODE else "T"
-        if have != preset:
-            raise RuntimeError("reference already loaded with preset %s in this process" % have)
-    elif preset in ("T", "D", "X"):
+        size = (const.ARENA_WIDTH, const.ARENA_HEIGHT)
+        if have != preset or size != (arena or ((800, 800) if const.GAME_MODE else (600, 600))):
+            raise RuntimeError("reference already loaded with preset %s at %d x %d in this process" % ((have,) + size))
+    elif preset in ("T", "D", "X"):  # (every id of ARENA is based on one of these)
         pkg = types.ModuleType("robo_rugby")
         pkg.__path__ = [os.path.join(REF_ROOT, "robo_rugby")]
         sub = types.ModuleType("robo_rugby.gym_env")
@@ -56,6 +65,11 @@ def load_reference(preset):
                 line = f"{name} = {was}"
                 assert text.count(line) == 1, line
                 text = text.replace(line, f"{name} = {want[name]}", 1)
+        if arena:
+            for name, value in zip(("ARENA_WIDTH", "ARENA_HEIGHT"), arena):
+                line = f"{name} = 800 if GAME_MODE else 600"
+                assert text.count(line) == 1, line
+                text = text.replace(line, f"{name} = {int(value)}", 1)
         const = types.ModuleType("robo_rugby.gym_env.RR_Constants")
         const.__file__ = path
         exec(compile(text, path, "exec"), const.__dict__)
@@ -75,6 +89,7 @@ def load_reference(preset):
     import robo_rugby.gym_env.RR_Observers as obs
     assert bool(const.GAME_MODE) == (preset in ("G", "D", "X"))
     assert const.NUM_ROBOTS_TOTAL == {"G": 4, "T": 1, "D": 2, "X": 3}[preset]
+    assert arena is None or (const.ARENA_WIDTH, const.ARENA_HEIGHT) == arena
     ns = types.SimpleNamespace(MyUtils=MyUtils, const=const, base=base, tp=tp, envs=envs, robot=robot,
-                               ball=ball, goal=goal, sk=sk, obs=obs, preset=preset)
+                               ball=ball, goal=goal, sk=sk, obs=obs, preset=ident)
     return ns

@@ -15,6 +15,8 @@ SRC = [os.path.join(HERE, "emu", "rr_hive_emu.cpp")] + [os.path.join(CSRC, f) fo
 PRESET_ID = {"T": 0, "G": 1, "D": 2, "X": 3}
 # lanes per arena the emulation is built for: the product's widths (csrc/rr_kstep.hpp; X: build.shape_lanes) and 64
 LANES = {"T": (2, 4, 64), "G": (8, 16, 32, 64), "D": (4, 64), "X": (8, 64)}
+for _wide, _shape in ol.SHAPE.items():  # the non-square ids run their shape's build at their own W, H
+    PRESET_ID[_wide], LANES[_wide] = PRESET_ID[_shape], LANES[_shape]
 
 
 def build():
@@ -115,3 +117,24 @@ def greedy_assign_batch(rxy, bxy, mask, W, H, dtype=np.float64):
         d[rows[ok], b[ok], :] = np.inf
         d[rows[ok], :, r[ok]] = np.inf
     return assign, near
+
+
+def random_layouts(rng, n, nr, nb, W, H):
+    """robots / balls in canonical layout (centres only matter): uniform over the arena, a third of the balls thrown into the goal
+    corners, and every 16th layout degenerate -- all balls in goals, or all but one"""
+    robots = np.zeros((n, nr, 10))
+    balls = np.zeros((n, nb, 8))
+    robots[:, :, 0] = rng.uniform(30, W - 30, (n, nr))
+    robots[:, :, 1] = rng.uniform(30, H - 30, (n, nr))
+    robots[:, :, 6] = rng.uniform(0, 360, (n, nr))
+    balls[:, :, 0] = rng.uniform(8, W - 8, (n, nb))
+    balls[:, :, 1] = rng.uniform(8, H - 8, (n, nb))
+    corner = rng.random((n, nb)) < 1 / 3
+    corner[::16] = True
+    keep_one = np.arange(n) % 32 == 16
+    corner[keep_one, rng.integers(0, nb, keep_one.sum())] = False
+    u, v = rng.uniform(0, 110, (n, nb)), rng.uniform(0, 110, (n, nb))  # u + v < 240: inside a triangle with legs of 240
+    far = rng.random((n, nb)) < .5
+    balls[:, :, 0] = np.where(corner, np.where(far, W - 5 - u, 5 + u), balls[:, :, 0])
+    balls[:, :, 1] = np.where(corner, np.where(far, H - 5 - v, 5 + v), balls[:, :, 1])
+    return robots, balls

@@ -19,7 +19,24 @@ PRESETS = {  # RR_Constants.py:6-7,24-25,30-34
     # a shape outside the library's built list (compiled on demand: roborugby_amd.build.build_shape_library): odd counts, unequal teams
     "X": dict(nr_h=2, nr_g=1, nb_p=2, nb_n=3, W=800.0, H=800.0, game_len=4500, game_mode=1),
     "Y": dict(nr_h=1, nr_g=1, nb_p=2, nb_n=1, W=800.0, H=800.0, game_len=4500, game_mode=1),  # four lanes per arena, three balls (emulation vs oracle only)
+    # non-square arenas: every other preset has W == H, where swapping the two anywhere changes nothing.  Dwide and Ttall are pinned to
+    # reference vectors (tests/golden/{traj,reset}_{Dwide,Ttall}.npz, mix_Dwide.npz: the reference with its two arena constants patched,
+    # oracle/refgen/load_reference.py); Gwide (G's counts) is for oracle-vs-emulation-vs-kernel comparisons only
+    "Dwide": dict(nr_h=1, nr_g=1, nb_p=1, nb_n=1, W=1000.0, H=640.0, game_len=4500, game_mode=1),
+    "Ttall": dict(nr_h=1, nr_g=0, nb_p=1, nb_n=0, W=480.0, H=720.0, game_len=300, game_mode=0),
+    "Gwide": dict(nr_h=2, nr_g=2, nb_p=4, nb_n=4, W=1000.0, H=640.0, game_len=4500, game_mode=1),
 }
+SHAPE = {"Dwide": "D", "Ttall": "T", "Gwide": "G"}  # the preset whose entity counts (= compiled shape) a non-square id has
+
+
+def product_preset(name):
+    """The product-side Preset of an id of PRESETS: the library's own for the square ones, its shape's with the arena size replaced for
+    the non-square ones (roborugby_amd.config keeps no entry for them)."""
+    import dataclasses
+    import roborugby_amd as rr
+    if name not in SHAPE:
+        return rr.PRESETS[name]
+    return dataclasses.replace(rr.PRESETS[SHAPE[name]], name=name, arena_w=PRESETS[name]["W"], arena_h=PRESETS[name]["H"])
 
 
 def build(force=False):

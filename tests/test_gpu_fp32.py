@@ -22,7 +22,7 @@ def _env(preset, n, dtype="f32", **kw):
     import roborugby_amd as rr
     kw.setdefault("time_limit", False)
     kw.setdefault("auto_reset", False)
-    return rr.BatchedRoboRugbyEnv(n, preset=preset, dtype=dtype, **kw)
+    return rr.BatchedRoboRugbyEnv(n, preset=ol.product_preset(preset), dtype=dtype, **kw)
 
 
 def _assert_state_mode(tag, q, e, ints, done_ok, pre, post, got, cfg):
@@ -72,10 +72,10 @@ def _assert_distribution(tag, q, e, ints, done_ok):
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f32_state"])
-@pytest.mark.parametrize("preset", ["T", "G"])
+@pytest.mark.parametrize("preset", ["T", "G", "Dwide"])
 def test_f32_single_step_vs_reference_golden(golden_dir, preset, dtype):
     """Every recorded reference step (tests/golden/traj_*.npz) replayed through an RR_DTYPE_F32 / RR_DTYPE_F32_STATE env from the
-    reference's dumped state."""
+    reference's dumped state.  Dwide: the 1000 x 640 arena -- the fp32 builds' walls, clamps and bounces at W != H, same bars."""
     t = np.load(f"{golden_dir}/traj_{preset}.npz")
     cfg = ol.PRESETS[preset]
     idx = [(ep, s) for ep in range(t["length"].shape[0]) for s in range(int(t["length"][ep]))]

@@ -20,7 +20,7 @@ def _env(preset, n, **kw):
     import roborugby_amd as rr
     kw.setdefault("time_limit", False)
     kw.setdefault("auto_reset", False)
-    return rr.BatchedRoboRugbyEnv(n, preset=preset, **kw)
+    return rr.BatchedRoboRugbyEnv(n, preset=ol.product_preset(preset), **kw)  # (Dwide, Ttall, Gwide: their shape's Preset at their W x H)
 
 
 def _flatten_golden(t):
@@ -34,11 +34,14 @@ def _flatten_golden(t):
     return pre, post, out
 
 
-@pytest.mark.parametrize("preset,exact", [(p, e) for p in ("T", "G", "D") for e in (False, True)] + [("X", False)],
+@pytest.mark.parametrize("preset,exact", [(p, e) for p in ("T", "G", "D") for e in (False, True)] + [("X", False)]
+                         + [("Dwide", False), ("Dwide", True), ("Ttall", False)],
                          ids=lambda v: {False: "default", True: "exact_trig"}.get(v, v) if isinstance(v, bool) else v)
 def test_step_matches_reference_golden_f64(golden_dir, preset, exact):
     """exact=True: the same bar for the exact-trig parity build (libroborugby_amd_exact.so).  Preset X (2 + 1 robots, 2 + 3 balls) is not
-    one of the shapes inside the library: it runs through the one-shape library compiled on demand (build.build_shape_library)."""
+    one of the shapes inside the library: it runs through the one-shape library compiled on demand (build.build_shape_library).
+    Dwide (1000 x 640) and Ttall (480 x 720) are the non-square arenas: every step that tells width from height -- walls, clamps, the
+    ball / wall bounce with the reference's width-for-height line, lidar, goal corner, reward multiplier -- at W != H."""
     t = np.load(f"{golden_dir}/traj_{preset}.npz")
     pre, post, out = _flatten_golden(t)
     n = pre["step"].shape[0]
@@ -77,6 +80,7 @@ def test_step_matches_reference_golden_f64(golden_dir, preset, exact):
         if "naughty" in out:  # the robots NaughtyBots flagged travel in status bits 16+: exact
             assert np.array_equal((status >> 16) & 0xFF, out["naughty"][sel])
         worst = max(worst, dr, db, do, drw)
+        print(f"[{preset}{' exact-trig build' if exact else ''}] {len(sel)} steps with {k} actions: robots {dr:.3e} balls {db:.3e} obs {do:.3e} rewards {drw:.3e}")
         assert dr < TOL64 and db < TOL64 and do < TOL64 and drw < 1e-7, (preset, k, dr, db, do, drw)
     print(f"[{preset}{' exact-trig build' if exact else ''}] {n} golden steps replayed on GPU, worst abs diff {worst:.3e}")
 
@@ -122,7 +126,7 @@ def test_thrust_entry_matches_reference_golden(golden_dir, preset):
     print(f"[{preset}] {len(idx)} golden thrust steps replayed on GPU, worst abs state diff {worst:.3e}")
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall", "Gwide"])
 def test_reset_matches_oracle_bit_exact(preset):
     """Same Philox stream + same rejection rule -> identical placements and first observations."""
     n, seed = 257, 1234
@@ -142,7 +146,7 @@ def test_reset_matches_oracle_bit_exact(preset):
     assert (st["step"] == 0).all()
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall"])
 def test_kernel_reset_distribution_matches_reference(golden_dir, preset):
     """The in-kernel reset (reset_arena, Philox) against the 1,000 layouts the imported reference's
     _set_random_positions produced (RR_EnvBase.py:155-200; tests/golden/reset_*.npz): 131,072 arenas constructed and

@@ -61,25 +61,7 @@ def test_emulated_kernel_reproduces_the_reference_hive(golden_dir, preset, vw):
             assert err <= 1e-9, (preset, vw, int(mask), kind, err)
 
 
-def _random_layouts(rng, n, nr, nb, W, H):
-    """robots / balls in canonical layout (centres only matter): uniform over the arena, a third of the balls thrown into the goal
-    corners, and every 16th layout degenerate -- all balls in goals, or all but one"""
-    robots = np.zeros((n, nr, 10))
-    balls = np.zeros((n, nb, 8))
-    robots[:, :, 0] = rng.uniform(30, W - 30, (n, nr))
-    robots[:, :, 1] = rng.uniform(30, H - 30, (n, nr))
-    robots[:, :, 6] = rng.uniform(0, 360, (n, nr))
-    balls[:, :, 0] = rng.uniform(8, W - 8, (n, nb))
-    balls[:, :, 1] = rng.uniform(8, H - 8, (n, nb))
-    corner = rng.random((n, nb)) < 1 / 3
-    corner[::16] = True
-    keep_one = np.arange(n) % 32 == 16
-    corner[keep_one, rng.integers(0, nb, keep_one.sum())] = False
-    u, v = rng.uniform(0, 110, (n, nb)), rng.uniform(0, 110, (n, nb))  # u + v < 240: inside a triangle with legs of 240
-    far = rng.random((n, nb)) < .5
-    balls[:, :, 0] = np.where(corner, np.where(far, W - 5 - u, 5 + u), balls[:, :, 0])
-    balls[:, :, 1] = np.where(corner, np.where(far, H - 5 - v, 5 + v), balls[:, :, 1])
-    return robots, balls
+_random_layouts = he.random_layouts
 
 
 @pytest.mark.parametrize("preset,vw,mask,n", [("G", 8, 0b0011, 6000), ("G", 8, 0b1111, 3000), ("G", 64, 0b1010, 1000), ("G", 16, 0b0100, 500),

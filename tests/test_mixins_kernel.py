@@ -15,7 +15,7 @@ def _close(a, b, tol=TOL):
     return np.array_equal(np.isnan(a), np.isnan(b)) and (np.nan_to_num(np.abs(a - b)).max() if a.size else 0.0) < tol
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide"])
 def test_emulated_side_kernels_vs_reference_golden(golden_dir, preset):
     t = np.load(f"{golden_dir}/mix_{preset}.npz")
     meta = json.loads(str(t["meta"]))
@@ -56,13 +56,14 @@ def test_keeper_exec_order_rule():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide"])
 def test_gpu_mixin_stacks_vs_reference_golden(golden_dir, preset):
     import torch
     import roborugby_amd as rr
     t = np.load(f"{golden_dir}/mix_{preset}.npz")
     meta = json.loads(str(t["meta"]))
-    nr = rr.PRESETS[preset].nr
+    preset = el.ol.product_preset(preset)  # Dwide: D's Preset at 1000 x 640
+    nr = preset.nr
     for which, stack in ((0, meta["programs_mro"]["A"]), (1, meta["programs_mro"]["B"])):
         eps = np.nonzero(t["which"] == which)[0]
         idx = [(ep, s) for ep in eps for s in range(int(t["length"][ep])) if (t["actions"][ep, s] >= 0).sum() == nr]
@@ -77,19 +78,19 @@ def test_gpu_mixin_stacks_vs_reference_golden(golden_dir, preset):
         for name, key, team in (("SingleBall_6wayLidar", "v1", 1), ("PosBall_BasicLidar", "basic", 1), ("AllCoords", "all", 1),
                                 ("AllCoords", "all", -1)):
             got = env.get_game_state(team, f64=True, observer=name).cpu().numpy()
-            assert _close(got, t[f"{key}_{'h' if team == 1 else 'g'}"][ep, st]), (preset, which, name, team)
+            assert _close(got, t[f"{key}_{'h' if team == 1 else 'g'}"][ep, st]), (preset.name, which, name, team)
         # AllCoords_WithPrior needs the on_step_begin snapshot: an env configured with that observer tracks it
         envp = rr.BatchedRoboRugbyEnv(len(idx), preset=preset, time_limit=False, auto_reset=False, rewards=tuple(stack),
                                       observer="AllCoords_WithPrior")
-        assert envp.observation_space.shape == (6 * nr + 4 * rr.PRESETS[preset].nb,)
+        assert envp.observation_space.shape == (6 * nr + 4 * preset.nb,)
         envp.set_state(t["state_robots"][ep, st], t["state_robots_i"][ep, st], t["state_balls"][ep, st], t["state_step"][ep, st])
         envp.step_f64(torch.as_tensor(t["actions"][ep, st].astype(np.int32)))
         for team in (1, -1):
             got = envp.get_game_state(team, f64=True).cpu().numpy()
-            assert _close(got, t[f"allp_{'h' if team == 1 else 'g'}"][ep, st]), (preset, which, "AllCoords_WithPrior", team)
+            assert _close(got, t[f"allp_{'h' if team == 1 else 'g'}"][ep, st]), (preset.name, which, "AllCoords_WithPrior", team)
         with pytest.raises(RuntimeError):
             env.get_game_state(1, observer="AllCoords_WithPrior")  # this env never asked for the snapshot
-        if rr.PRESETS[preset].nr_grumpy > 0:
+        if preset.nr_grumpy > 0:
             got = env.get_game_state(-1, f64=True, observer="SingleBall_6wayLidar").cpu().numpy()
             assert _close(got, t["v1_g"][ep, st])
         else:

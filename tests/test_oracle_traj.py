@@ -66,8 +66,9 @@ def _drive(env, t, ep, s):
     return env.step(acts[acts >= 0])
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall"])
 def test_trajectories_bit_exact(golden_dir, preset):
+    """Dwide / Ttall: the non-square arenas (1000 x 640, 480 x 720), where a swapped width and height anywhere in the step shows."""
     t = np.load(f"{golden_dir}/traj_{preset}.npz")
     total = 0
     for ep in range(t["length"].shape[0]):
@@ -77,6 +78,8 @@ def test_trajectories_bit_exact(golden_dir, preset):
     # the fixtures really exercise every response path of the hot loop
     for k in ("apply_force_to_ball", "bounce_ball_off_bot", "bounce_ball_off_wall", "undo_naughty"):
         assert cov[k] > 0, k
+    if preset == "Dwide":
+        assert cov["robot_collision"] > 0
     if preset in ("G", "X"):
         assert cov["bounce_balls"] > 0 and cov["robot_collision"] > 0
 

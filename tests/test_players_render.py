@@ -35,6 +35,22 @@ def test_debug_render_shapes_and_marks():
     assert abs(max(x for x, _ in c) - 20) < 1e-9 and abs(max(y for _, y in c) - 10) < 1e-9
 
 
+def test_debug_render_of_a_non_square_arena():
+    """1000 x 640: the picture is H rows by W + 300 (dashboard strip) columns, and the happy goal sits in the corner at (W, H)."""
+    import dataclasses
+    p = dataclasses.replace(PRESETS["D"], arena_w=1000.0, arena_h=640.0)
+    robots = np.zeros((2, 10))
+    robots[:, 0] = [300, 500]
+    robots[:, 1] = 320
+    balls = np.zeros((2, 8))
+    balls[:, :2] = [(900, 100), (100, 600)]
+    img = draw_arena(p, robots, balls)
+    assert img.shape == (640, 1300, 3) and img.dtype == np.uint8
+    assert tuple(img[640 - 5, 1000 - 5]) == (43, 146, 228) and tuple(img[5, 5]) == (242, 53, 87)  # img[y, x]: happy goal at (W - 5, H - 5)
+    assert tuple(img[100, 900]) == (80, 220, 100) and tuple(img[600, 100]) == (60, 16, 83)        # balls at their own (x, y)
+    assert tuple(img[1000 - 5 - 640, 5]) != (43, 146, 228)                                      # nothing of the goal where (H, W) would put it
+
+
 @pytest.mark.gpu
 def test_thrust_action_mode_and_render_on_gpu():
     import roborugby_amd as rr

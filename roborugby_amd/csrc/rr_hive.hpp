@@ -41,7 +41,7 @@ template <int VW, typename R> inline void vw_argmin(R (&d)[VW], int (&p)[VW]) {
 //   (a) one lane per ball: candidate? (ballot) ; one lane per (ball, robot) pair, pair = ball * NR + robot: the distance, in registers
 //   (b) at most min(NR, NB) rounds: every lane's best free pair, arg-min across the lanes, the winner's robot and ball are taken
 template <class C>
-RR_HDN void hive_assign(const Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t robot_mask, uint32_t &got, uint64_t &which) {
+RR_HD void hive_assign(const Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t robot_mask, uint32_t &got, uint64_t &which) {
     using R = typename C::Real;
     constexpr int NP = C::NR * C::NB, KP = (NP + C::VW - 1) / C::VW; // pairs per lane
     constexpr int ROUNDS = C::NR < C::NB ? C::NR : C::NB;
@@ -108,7 +108,7 @@ RR_HDN void hive_assign(const Arena<C> &A, const SimParams<typename C::Real> &sp
 // robots spread over the arena's lanes (q = the arena's record).  Rows of robots without a ball are 0.
 // (KIND is a template parameter: a kernel that holds both observers needs every register the file has.)
 template <class C, typename O, int KIND>
-RR_HDN void hive_observe(Arena<C> &A, const Rec<C> &q, const SimParams<typename C::Real> &sp, uint32_t robot_mask, int32_t *assign,
+RR_HD void hive_observe(Arena<C> &A, const Rec<C> &q, const SimParams<typename C::Real> &sp, uint32_t robot_mask, int32_t *assign,
                          O *obs) {
     uint32_t got;
     uint64_t which;

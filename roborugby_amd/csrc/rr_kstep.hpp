@@ -45,19 +45,12 @@ template <class C> __device__ __forceinline__ void store_record(const Arena<C> &
 #define RR_WAVES_PER_BLOCK 1 // arenas never cooperate across wavefronts, so a workgroup IS a wavefront (finer dispatch: +9 % measured)
 #endif
 constexpr int WAVES_PER_BLOCK = RR_WAVES_PER_BLOCK;
-#ifdef RR_ARENAS_PER_WAVE // occupancy probe only: fewer arenas per wavefront (idle lanes) so that LDS admits a third wave per SIMD
-template <class C> constexpr int arenas_per_block() { return (C::VW == 8 ? RR_ARENAS_PER_WAVE : 64 / C::VW) * WAVES_PER_BLOCK; }
-#else
 template <class C> constexpr int arenas_per_block() { return 64 * WAVES_PER_BLOCK / C::VW; }
-#endif
 // Waves per SIMD the 160 KiB of LDS admit for this configuration.  Asking the register allocator for more than that
 // (launch bounds) only buys spills: with 17 KB of LDS per wavefront G/VW=8 and T/VW=2 top out at 2 waves/SIMD, and
 // capping them at 128 VGPRs put ~30 scratch round trips into every sub-step (measured: 487 VMEM instructions per
 // wave-step instead of ~90, and a 0.25 ms latency floor per launch).
 template <class C> constexpr int lds_waves_per_simd() {
-#ifdef RR_FORCE_WAVES // occupancy experiments only (tools/kernel_resources.py ... -DRR_FORCE_WAVES=3)
-    return RR_FORCE_WAVES;
-#endif
     constexpr int per_cu = (160 * 1024) / (int)(sizeof(Arena<C>) * arenas_per_block<C>()) * WAVES_PER_BLOCK;
     return per_cu / 4 < 1 ? 1 : (per_cu / 4 > RR_MIN_WAVES_PER_SIMD ? RR_MIN_WAVES_PER_SIMD : per_cu / 4);
 }
@@ -75,15 +68,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
                                                               uint32_t *snap, int32_t *isnap, uint32_t *park = nullptr,
                                                               uint32_t budget = 0) {
     static_assert(!(MULTI && BUDGET), "rr_rollout keeps the record in LDS across steps: no barrier to budget");
-#ifdef RR_FAKE_LDS_ARENAS // resource experiments only (never run): what the register allocator does when LDS stops capping the occupancy
-    __shared__ Arena<C> lds[RR_FAKE_LDS_ARENAS];
-#else
     __shared__ Arena<C> lds[arenas_per_block<C>()];
-#endif
     const int wave = threadIdx.x / C::VW; // virtual wave = arena slot in this workgroup
-#ifdef RR_ARENAS_PER_WAVE
-    if (wave >= arenas_per_block<C>()) return;
-#endif
     // slowest-first dispatch: workgroup b steps the group of arenas that was the b-th slowest in the previous step
     const unsigned long long t_begin = (cost || BUDGET) ? __builtin_amdgcn_s_memtime() : 0ull;
     const int group = order ? (int)order[blockIdx.x] : (int)blockIdx.x;

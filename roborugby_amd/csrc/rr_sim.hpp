@@ -31,17 +31,11 @@
 #endif
 
 #if defined(__HIPCC__)
-#define RR_HD __host__ __device__ __forceinline__
-// rarely-taken paths (contact responses, reset).  Measured on MI355X: inlining them too and capping registers
+// everything is inlined, the rarely-taken paths (contact responses, reset) too.  Measured on MI355X: inlining them and capping registers
 // with __launch_bounds__ (4 waves/SIMD) beats real calls, whose ABI pins values in high callee-saved VGPRs.
-#ifdef RR_OUTLINE_RARE
-#define RR_HDN __host__ __device__ __noinline__
-#else
-#define RR_HDN __host__ __device__ __forceinline__
-#endif
+#define RR_HD __host__ __device__ __forceinline__
 #else
 #define RR_HD inline
-#define RR_HDN
 #endif
 
 // A wavefront is split into 64/VW "virtual waves" of VW lanes (C::VW, a power of two); each owns one arena.
@@ -109,20 +103,11 @@ __device__ unsigned long long g_rr_wave_t[2 * 65536]; // [start, end] s_memtime 
 #endif
 
 // The frozen island's "witness" tests (substep): default build only -- in the parity build every extra detection sweep would walk the
-// reference's scratch rect.  -DRR_NO_WITNESS: A/B builds.
-#if defined(RR_NO_WITNESS)
-#define RR_WITNESS 0
-#else
+// reference's scratch rect.
 #define RR_WITNESS (!RR_CARRY)
-#endif
 // rare branches (contact paths, reset, frozen islands): tells the register allocator where spilling is cheap
 #define RR_UNLIKELY(x) __builtin_expect(!!(x), 0)
 
-#ifdef RR_NO_OBS_STAGE // A/B builds only: observation rows written by one lane, value by value
-#define RR_OBS_STAGE 0
-#else
-#define RR_OBS_STAGE 1
-#endif
 #ifndef RR_NUM_SUBSTEPS
 #define RR_NUM_SUBSTEPS 12 // MOVES_PER_FRAME (RR_Constants.py:13); only the emulation harness overrides it to bisect
 #endif
@@ -178,12 +163,6 @@ RR_HD float m_rint(float x) { return ::rintf(x); }
 // configurations are parity modes -- BatchedRoboRugbyEnv refuses exact_trig with dtype f32.)
 #ifndef RR_CARRY
 #define RR_CARRY RR_EXACT_TRIG
-#endif
-// phase 1's broad tests: after the radius bounds, also the separating-axis / robot-frame bounds (with the motion slack), so that fewer
-// wavefronts enter the reference-shaped loops for pairs that merely pass each other.  A/B only: G -4 %, T -1 % (the extra tests
-// cost the hot phase more than the skipped loops save; profiles/r03/broad_tight_ab.txt) -- the frozen variants always use them.
-#ifndef RR_BROAD_TIGHT
-#define RR_BROAD_TIGHT 0
 #endif
 #if RR_EXACT_TRIG
 // The "exact trig" build (libroborugby_amd_exact.so, BatchedRoboRugbyEnv(exact_trig=True)): sin & cos to ~2^-63 of their true values
@@ -456,9 +435,6 @@ template <class C> struct ArenaBody {
 #if RR_CARRY
         R ic[2];  // centre of the reference's scratch rect _rectBallInner as its last user left it ("scratch-rect carry")
 #endif
-#ifdef RR_REL_IN_RECORD // A/B builds only: the corner offsets travel with the record instead of being rebuilt by derive()
-        R rel[NR][9];
-#endif
     } p;
     struct I {
         int32_t mc[NR], thl[NR], thr[NR];
@@ -467,9 +443,7 @@ template <class C> struct ArenaBody {
     } i;
     // ---- per-step scratch
     // (rows of 9, not 8: a 16-word row stride would put every robot's row of every arena of a bank group on the same 4 banks)
-#ifndef RR_REL_IN_RECORD
     R rel[NR][9];   // corner offsets TL,TR,BL,BR (x,y) for the current rotation
-#endif
     R irot[NR];     // rotation irel was built for (NaN = stale)
     R sm[NR][4], sc[NR][4]; // slope / y-intercept of the four sides (get_slope_yint, MyUtils.py:44-58) for the current pose
     R ax[NR], ay[NR], arot[NR]; // pose at frame begin (= ring entry written this frame)
@@ -494,9 +468,6 @@ template <class C> struct ArenaBody {
         R lidar[2][3 * NR];               // [front|back][ray, rect] minima over the rect's four sides
     } u;
     R lid[6];                             // capped minima: front/back per ray
-#ifdef RR_LDS_EXTRA
-    R extra_[NR > 1 ? RR_LDS_EXTRA : 1]; // occupancy experiments only
-#endif
     static constexpr int P_REALS = (int)(sizeof(P) / sizeof(R));
     static constexpr int I_INTS = (int)(sizeof(I) / sizeof(int32_t));
     // HBM record of one arena: the P reals, the I ints right behind them, padded to a 64-B multiple (so that the lane-strided
@@ -521,9 +492,6 @@ template <class C> struct ArenaBody {
 // when stride = win * (odd number).  G/fp64/VW=8 was 576 words = 9 * 64: every arena on the same banks, 4-way
 // conflicts on every access (SQ_LDS_BANK_CONFLICT = 4x the LDS instruction cycles).  VW >= 32: one arena per group.
 constexpr int lds_pad_words(int body_words, int vw, int real_words) {
-#ifdef RR_NO_LDS_PAD // A/B builds only
-    return 0;
-#endif
     if (vw >= 32) return 0;
     const int win = vw * real_words;
     int pad = (win - body_words % win) % win;
@@ -577,11 +545,6 @@ template <class C> struct RecLayout {
                   "episode .. fault are 5 consecutive ints (k_episode_state)");
 };
 
-#ifdef RR_REL_IN_RECORD
-#define RR_REL(A) (A).p.rel
-#else
-#define RR_REL(A) (A).rel
-#endif
 // ------------------------------------------------------------------------------------------------ FloatRect in registers
 template <typename R> struct FR {
     R cx, cy, l, r, t, b, rot;
@@ -649,17 +612,17 @@ template <class C> RR_HD FR<typename C::Real> load_robot(const Arena<C> &A, int 
     FR<typename C::Real> f;
     f.cx = A.p.rcx[r]; f.cy = A.p.rcy[r]; f.l = A.p.rl[r]; f.r = A.p.rrt[r]; f.t = A.p.rt[r]; f.b = A.p.rb[r];
     f.rot = A.p.rrot[r];
-    for (int k = 0; k < 8; k++) f.rel[k] = RR_REL(A)[r][k];
+    for (int k = 0; k < 8; k++) f.rel[k] = A.rel[r][k];
     return f;
 }
 template <class C> RR_HD void store_robot(Arena<C> &A, int r, const FR<typename C::Real> &f) {
     A.p.rcx[r] = f.cx; A.p.rcy[r] = f.cy; A.p.rl[r] = f.l; A.p.rrt[r] = f.r; A.p.rt[r] = f.t; A.p.rb[r] = f.b;
     A.p.rrot[r] = f.rot;
-    for (int k = 0; k < 8; k++) RR_REL(A)[r][k] = f.rel[k];
+    for (int k = 0; k < 8; k++) A.rel[r][k] = f.rel[k];
     A.sides_ok = 0;
 }
 template <class C> RR_HD V2<typename C::Real> robot_corner(const Arena<C> &A, int r, int c) {
-    V2<typename C::Real> v = { A.p.rcx[r] + RR_REL(A)[r][2 * c], A.p.rcy[r] + RR_REL(A)[r][2 * c + 1] };
+    V2<typename C::Real> v = { A.p.rcx[r] + A.rel[r][2 * c], A.p.rcy[r] + A.rel[r][2 * c + 1] };
     return v;
 }
 template <class C> RR_HD Seg<typename C::Real> robot_side(const Arena<C> &A, int r, int s) {
@@ -749,7 +712,7 @@ RR_HD void robot_move_finish(Arena<C> &A, const SimParams<typename C::Real> &sp,
             if (nr != f.rot) {
                 f.rot = nr;
                 if (nr == rot_prior) {
-                    for (int k = 0; k < 8; k++) f.rel[k] = RR_REL(A)[r][k];
+                    for (int k = 0; k < 8; k++) f.rel[k] = A.rel[r][k];
                 } else {
                     corners_for<R>(nr, (R)10, (R)20, sp.rob_cdist, f.rel);
                 }
@@ -833,7 +796,7 @@ template <class C> RR_HD bool ball_near_robot(const Arena<C> &A, int b, int r) {
     using R = typename C::Real;
     const R dx = A.p.bcx[b] - A.p.rcx[r], dy = A.p.bcy[b] - A.p.rcy[r];
     if (!(dx * dx + dy * dy <= cull_br2<R>())) return false;
-    const R *q = RR_REL(A)[r];
+    const R *q = A.rel[r];
     const R ux = (q[2] - q[0]) * (R)0.05, uy = (q[3] - q[1]) * (R)0.05;     // TL -> TR, 20 long
     const R vx = (q[4] - q[0]) * (R)0.025, vy = (q[5] - q[1]) * (R)0.025;   // TL -> BL, 40 long
     const R lx = dx * ux + dy * uy, ly = dx * vx + dy * vy;
@@ -856,7 +819,7 @@ template <class C> RR_HD bool ball_near_robot(const Arena<C> &A, int b, int r) {
 template <class C>
 RR_HD bool robots_separated(const Arena<C> &A, int i, int j, typename C::Real dx, typename C::Real dy, typename C::Real m = (typename C::Real)0.05) {
     using R = typename C::Real;
-    const R *p = RR_REL(A)[i], *q = RR_REL(A)[j];
+    const R *p = A.rel[i], *q = A.rel[j];
     // unit axes (to ~1e-15) from the corner offsets: TL -> TR is 20 long, TL -> BL 40
     const R uix = (p[2] - p[0]) * (R)0.05, uiy = (p[3] - p[1]) * (R)0.05, vix = (p[4] - p[0]) * (R)0.025, viy = (p[5] - p[1]) * (R)0.025;
     const R ujx = (q[2] - q[0]) * (R)0.05, ujy = (q[3] - q[1]) * (R)0.05, vjx = (q[4] - q[0]) * (R)0.025, vjy = (q[5] - q[1]) * (R)0.025;
@@ -1278,7 +1241,7 @@ RR_HD PrevPose<typename C::Real> robot_prev_frame(const Arena<C> &A, const SimPa
         // same rotation value as the live rect (a robot driving straight, or one that has not turned since): the setter
         // returns early and the copy keeps the live corners -- which ARE corners_for(rrot): every writer of A.rel builds
         // it with that very expression -- so no trigonometry here.  The common case of a robot pushing a ball.
-        q.tlx = RR_REL(A)[r][0]; q.tly = RR_REL(A)[r][1]; q.trx = RR_REL(A)[r][2]; q.try_ = RR_REL(A)[r][3];
+        q.tlx = A.rel[r][0]; q.tly = A.rel[r][1]; q.trx = A.rel[r][2]; q.try_ = A.rel[r][3];
     } else {
         R rel[8];
         corners_for<R>(nr, (R)10, (R)20, sp.rob_cdist, rel);
@@ -1388,7 +1351,7 @@ RR_HD int first_corner_hit(Arena<C> &A, int r, V2<typename C::Real> bc, typename
 }
 // apply_force_to_ball (RR_TrashyPhysics.py:88-152)
 // (kpre: the surface search's result when the caller already has it, -2 = search here)
-template <class C> RR_HDN void apply_force_to_ball(Arena<C> &A, const SimParams<typename C::Real> &sp, int r, int b, uint32_t bots_moved, int &st, int kpre = -2) {
+template <class C> RR_HD void apply_force_to_ball(Arena<C> &A, const SimParams<typename C::Real> &sp, int r, int b, uint32_t bots_moved, int &st, int kpre = -2) {
     using R = typename C::Real;
     const R cbuf = (R).5;
     V2<R> bc = { A.p.bcx[b], A.p.bcy[b] }, rc = { A.p.rcx[r], A.p.rcy[r] };
@@ -1444,7 +1407,7 @@ template <typename R> RR_HD void bounce_reflect(V2<R> con, R &vx, R &vy, R &d2) 
     if ((pry < (R)0 && con.y > (R)0) || (pry > (R)0 && con.y < (R)0)) vy = -pry * (R).8 * (R).8;
 }
 // bounce_ball_off_bot (RR_TrashyPhysics.py:155-245)
-template <class C> RR_HDN void bounce_ball_off_bot(Arena<C> &A, const SimParams<typename C::Real> &sp, int r, int b, uint32_t bots_moved, int &st, int kpre = -2) {
+template <class C> RR_HD void bounce_ball_off_bot(Arena<C> &A, const SimParams<typename C::Real> &sp, int r, int b, uint32_t bots_moved, int &st, int kpre = -2) {
     using R = typename C::Real;
     R vx = A.p.bvx[b], vy = A.p.bvy[b];
     if (vx == (R)0 && vy == (R)0) return;
@@ -1643,7 +1606,7 @@ RR_HD void pv_robot_prev_frame(const Arena<C> &A, const SimParams<typename C::Re
     }
     const R nr = norm360<R>(rot);
     if (nr == A.p.rrot[r]) {
-        tl = pv_ld2<R>(&RR_REL(A)[r][0], 1, 0, l); tr = pv_ld2<R>(&RR_REL(A)[r][2], 1, 0, l);
+        tl = pv_ld2<R>(&A.rel[r][0], 1, 0, l); tr = pv_ld2<R>(&A.rel[r][2], 1, 0, l);
     } else {
         R rel[8];
         corners_for<R>(nr, (R)10, (R)20, sp.rob_cdist, rel);
@@ -1651,13 +1614,8 @@ RR_HD void pv_robot_prev_frame(const Arena<C> &A, const SimParams<typename C::Re
     }
 }
 template <typename R> RR_HD R pv_prev_off(int c, R tl, R tr) { return (c == TL) ? tl : (c == TR) ? tr : (c == BL) ? -tr : -tl; } // BR = -TL, BL = -TR
-#ifndef RR_NO_CBR
-#define RR_CBR 1
-#else
-#define RR_CBR 0 // A/B builds only: the resolve pass applies its ball-robot bounces one after the other (bounce_ball_off_bot)
-#endif
 template <class C>
-RR_HDN void bounce_pass(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t br, uint32_t bots_moved, int &st) {
+RR_HD void bounce_pass(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t br, uint32_t bots_moved, int &st) {
     using R = typename C::Real;
     constexpr int NR = C::NR, NB = C::NB, VW = C::VW;
     static_assert(VW >= 2 && (VW & 1) == 0, "lane pairs");
@@ -1854,7 +1812,7 @@ RR_HDN void bounce_pass(Arena<C> &A, const SimParams<typename C::Real> &sp, uint
                         }
                     } else {
                         if ((l & (G - 1)) == 0) RR_TRACE("E bounce corner c=%d b=%d r=%d\n", cn, b, r);
-                        const PV<R> rc = pv_ld2<R>(&A.p.rcx[0], NR, r, l), ro = pv_ld2<R>(&RR_REL(A)[r][2 * cn], 1, 0, l);
+                        const PV<R> rc = pv_ld2<R>(&A.p.rcx[0], NR, r, l), ro = pv_ld2<R>(&A.rel[r][2 * cn], 1, 0, l);
                         PV<R> con, pc, sq;
                         RR_PV_EACH(i) {
                             const R bcn = rc.v[i] + ro.v[i];
@@ -1905,63 +1863,12 @@ RR_HDN void bounce_pass(Arena<C> &A, const SimParams<typename C::Real> &sp, uint
         RR_SYNC();
     }
 }
-// bounce_balls (RR_TrashyPhysics.py:248-316)
-template <class C> RR_HDN void bounce_balls(Arena<C> &A, int i, int j, int &st) {
-    using R = typename C::Real;
-    R x1 = A.p.bcx[i], y1 = A.p.bcy[i], x2 = A.p.bcx[j], y2 = A.p.bcy[j];
-    if (x1 == x2 && y1 == y2) { st |= ST_SAME_SPOT; return; }
-    R vxx = x2 - x1, vyy = y2 - y1;
-    R d12 = m_sqrt(vxx * vxx + vyy * vyy);
-    R rx = vxx * (R)7 / d12, ry = vyy * (R)7 / d12;
-    R p1x = x1 + rx, p1y = y1 + ry, p2x = x2 - rx, p2y = y2 - ry;
-    const R buffer = (R)1.1;
-    R hx = (p2x - p1x) / (R)2, hy = (p2y - p1y) / (R)2;
-    int m1 = A.bmass[i], m2 = A.bmass[j];
-    R n1x = x1, n1y = y1, n2x = x2, n2y = y2;
-    if (m1 == m2) {
-        n1x = x1 + hx * buffer; n1y = y1 + hy * buffer;
-        n2x = x2 - hx * buffer; n2y = y2 - hy * buffer;
-    } else if (m1 > m2) {
-        n2x = x2 + (p1x - p2x) * buffer; n2y = y2 + (p1y - p2y) * buffer;
-        m2 = m1;
-    } else {
-        n1x = x1 + (p2x - p1x) * buffer; n1y = y1 + (p2y - p1y) * buffer;
-        m1 = m2;
-    }
-    // centre setters are incremental: new centre = c + (n - c)
-    R c1x = x1 + (n1x - x1), c1y = y1 + (n1y - y1), c2x = x2 + (n2x - x2), c2y = y2 + (n2y - y2);
-    R ax = c2x - c1x, ay = c2y - c1y;          // tplVect1to2
-    R bx = ax * (R)-1, by = ay * (R)-1;          // tplVect2to1
-    R d2 = ax * ax + ay * ay;
-    R v1x = A.p.bvx[i], v1y = A.p.bvy[i], v2x = A.p.bvx[j], v2y = A.p.bvy[j];
-    R t1 = div0<R>(ax * v1x + ay * v1y, d2, st);
-    R t2 = div0<R>(bx * v2x + by * v2y, d2, st);
-    R dfx = t1 * ax - t2 * bx, dfy = t1 * ay - t2 * by;
-    v1x -= dfx * (R).995; v1y -= dfy * (R).995;
-    v2x += dfx * (R).995; v2y += dfy * (R).995;
-    R f1x = A.bfx[i], f1y = A.bfy[i], f2x = A.bfx[j], f2y = A.bfy[j];
-    if (f1x > (R)0) v1x = py_max<R>(v1x, f1x); else if (f1x < (R)0) v1x = py_min<R>(v1x, f1x);
-    if (f1y > (R)0) v1y = py_max<R>(v1y, f1y); else if (f1y < (R)0) v1y = py_min<R>(v1y, f1y);
-    if (f2x > (R)0) v2x = py_max<R>(v2x, f2x); else if (f2x < (R)0) v2x = py_min<R>(v2x, f2x);
-    if (f2y > (R)0) v2y = py_max<R>(v2y, f2y); else if (f2y < (R)0) v2y = py_min<R>(v2y, f2y);
-    if (RR_IS_LANE0) {
-        // an unmoved ball gets a zero delta, which leaves its rect bit-identical
-        ball_shift(A, i, n1x - x1, (R)0);
-        ball_shift(A, i, (R)0, n1y - y1);
-        ball_shift(A, j, n2x - x2, (R)0);
-        ball_shift(A, j, (R)0, n2y - y2);
-        A.bmass[i] = m1; A.bmass[j] = m2;
-        A.p.bvx[i] = v1x; A.p.bvy[i] = v1y; A.p.bvx[j] = v2x; A.p.bvy[j] = v2y;
-        ball_exc_update(A, i); ball_exc_update(A, j);
-    }
-    RR_SYNC();
-}
 // The ball-ball bounces of one resolve pass (RR_EnvBase.py:373-378: `for ball1, ball2 in collisions: bounce_balls`), on lane pairs.
 // A bounce reads and writes its two balls only, so consecutive bounces of the (frozen, ordered) hit list that share no ball are
 // independent: the list is cut into maximal runs of mutually disjoint pairs, a run's bounces go side by side -- one lane pair
 // each -- and the runs follow each other in list order.  Inside a bounce the even lane holds the x components, the odd lane the y
-// components (bounce_balls above, operation for operation; the two projections t1 | t2 are one division on either lane).
-template <class C> RR_HDN void bounce_balls_pass(Arena<C> &A, uint64_t bbm, int &st) {
+// components (the reference's bounce_balls, RR_TrashyPhysics.py:248-316, operation for operation; the two projections t1 | t2 are one division on either lane).
+template <class C> RR_HD void bounce_balls_pass(Arena<C> &A, uint64_t bbm, int &st) {
     using R = typename C::Real;
     constexpr int NB = C::NB, VW = C::VW;
     (void)sizeof(PairFields<C>);
@@ -2149,7 +2056,7 @@ struct MidState {
 
 // ------------------------------------------------------------------------------------------------ sub-step pieces (RR_EnvBase.py:303-454)
 // returns whether any pair collided (i.e. whether any robot may have been put back)
-template <class C> RR_HDN bool resolve_bot_collisions(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t &bots_moved, uint32_t &naughty, int &st, int &work, Hit &hit) {
+template <class C> RR_HD bool resolve_bot_collisions(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t &bots_moved, uint32_t &naughty, int &st, int &work, Hit &hit) {
     if (C::NPR == 0) return false;
     uint32_t pairs = detect_robot_pairs(A);
     if (!pairs) return false;
@@ -2182,7 +2089,7 @@ template <class C> RR_HDN bool resolve_bot_collisions(Arena<C> &A, const SimPara
 // returns 1 (resolved), 0 (gave up after 10 passes) or, budgeted step only, -1: over the budget between two passes -- `count` passes are
 // done, the caller parks the arena and a later call re-enters here with count0 = count (at least one pass runs per entry)
 template <class C, bool BUDGET = false>
-RR_HDN int resolve_ball_collisions(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t bots_moved, int &st, int &work, Hit &hit,
+RR_HD int resolve_ball_collisions(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t bots_moved, int &st, int &work, Hit &hit,
                                    int count0 = 0, const ParkCtx *pk = nullptr, int *count_out = nullptr) {
     bool naughty = true;
     int count = count0;
@@ -2199,7 +2106,6 @@ RR_HDN int resolve_ball_collisions(Arena<C> &A, const SimParams<typename C::Real
         if (count > 10) { RR_TRACE("E resolve gave up\n"); return 0; }
         naughty = false;
         uint64_t bb = detect_ball_pairs(A);
-#if RR_CBR
         if (bb) {
             naughty = true;
 #pragma unroll 1
@@ -2211,22 +2117,10 @@ RR_HDN int resolve_ball_collisions(Arena<C> &A, const SimParams<typename C::Real
             }
             bounce_balls_pass(A, bb, st);
         }
-#else
-#pragma unroll 1
-        for (uint64_t todo = bb; todo; todo &= todo - 1) {
-            int i, j;
-            pair_of<C>(low_bit(todo), C::NB, i, j);
-            RR_TRACE("E pass %d bb %d %d\n", count, i, j);
-            hit.b |= (1u << i) | (1u << j);
-            naughty = true;
-            bounce_balls(A, i, j, st);
-        }
-#endif
         RR_STAMP(14);
         // caches already built in this sub-step (a hit in the push or in an earlier pass)?  then the cheap variant
         uint32_t br = A.sides_ok ? detect_ball_robot<C, true>(A, sp) : detect_ball_robot<C, false>(A, sp);
         RR_STAMP(15);
-#if RR_CBR
         if (br) {
             naughty = true;
             for (int b = 0; b < C::NB; b++) {
@@ -2240,15 +2134,6 @@ RR_HDN int resolve_ball_collisions(Arena<C> &A, const SimParams<typename C::Real
             bounce_pass(A, sp, br, bots_moved, st); // the bounces of different balls side by side
 #endif
         }
-#else
-#pragma unroll 1
-        for (uint32_t todo = br; todo; todo &= todo - 1) {
-            const int p = low_bit(todo);
-            naughty = true;
-            hit.b |= 1u << (p / C::NR); hit.r |= 1u << (p % C::NR);
-            bounce_ball_off_bot(A, sp, p % C::NR, p / C::NR, bots_moved, st);
-        }
-#endif
         RR_STAMP(16);
         uint32_t bw = detect_ball_wall(A, sp);
         if (bw) {
@@ -2272,7 +2157,7 @@ RR_HDN int resolve_ball_collisions(Arena<C> &A, const SimParams<typename C::Real
     return 1;
 }
 template <class C>
-RR_HDN void undo_naughty_movement(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t &balls_moved,
+RR_HD void undo_naughty_movement(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t &balls_moved,
                                  uint32_t &bots_moved, int &st, Hit &hit) {
     bool naughty = true;
     int count = 0;
@@ -2357,7 +2242,7 @@ RR_HD void substep_phase1(Arena<C> &A, const SimParams<typename C::Real> &sp, co
                 // (frozen variant only -- it costs the common path nothing: a spurious "close" thaws the island, so the pair also
                 // has to pass the separating-axis test, grown by the 2 x 3 px the two robots can still move; every robot is
                 // still on its frame-begin pose here)
-                if ((FZ || RR_BROAD_TIGHT) && PAIRED && cl) cl = !robots_separated(A, r, j, dx, dy, (R)6.05);
+                if (FZ && PAIRED && cl) cl = !robots_separated(A, r, j, dx, dy, (R)6.05);
                 c_rr = c_rr | cl;
             }
             if (!PAIRED) { // _move_bots
@@ -2388,8 +2273,8 @@ RR_HD void substep_phase1(Arena<C> &A, const SimParams<typename C::Real> &sp, co
                 for (int r2 = 0; r2 < C::NR; r2++) { // ball-robot: 22.36 + 9.9 (+ 3 px of robot motion)
                     R dx = A.p.bcx[l] - A.p.rcx[r2], dy = A.p.bcy[l] - A.p.rcy[r2];
                     bool cl = dx * dx + dy * dy <= (R)(36.0 * 36.0);
-                    if ((FZ || RR_BROAD_TIGHT) && PAIRED && cl) { // the robot-frame bound of ball_near_robot, grown by the same 3 px
-                        const R *q = RR_REL(A)[r2];
+                    if (FZ && PAIRED && cl) { // the robot-frame bound of ball_near_robot, grown by the same 3 px
+                        const R *q = A.rel[r2];
                         const R ux = (q[2] - q[0]) * (R)0.05, uy = (q[3] - q[1]) * (R)0.05, vx = (q[4] - q[0]) * (R)0.025, vy = (q[5] - q[1]) * (R)0.025;
                         cl = (m_abs(dx * ux + dy * uy) <= (R)20.05) & (m_abs(dx * vx + dy * vy) <= (R)30.05);
                     }
@@ -2650,7 +2535,7 @@ RR_HD bool substep(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t 
             if (hitw) { // the reference's undo loop would have found this contact: back to the moved poses, then the full path
                 RR_FOR_LANES(l) {
                     if (l < C::NR && ((fz.r >> l) & 1u)) {
-                        if (A.p.rrot[l] != RR_LV(w6, l)) corners_for<R>(RR_LV(w6, l), (R)10, (R)20, sp.rob_cdist, RR_REL(A)[l]);
+                        if (A.p.rrot[l] != RR_LV(w6, l)) corners_for<R>(RR_LV(w6, l), (R)10, (R)20, sp.rob_cdist, A.rel[l]);
                         A.p.rcx[l] = RR_LV(w0, l); A.p.rcy[l] = RR_LV(w1, l); A.p.rl[l] = RR_LV(w2, l); A.p.rrt[l] = RR_LV(w3, l);
                         A.p.rt[l] = RR_LV(w4, l); A.p.rb[l] = RR_LV(w5, l); A.p.rrot[l] = RR_LV(w6, l);
                         A.i.mc[l] += 1;
@@ -2745,9 +2630,79 @@ template <class C> RR_HD void substeps_end(Arena<C> &A, uint32_t prev_moved) {
 }
 
 // ------------------------------------------------------------------------------------------------ observation (RR_Observers.py:301-406)
-// lidar: one lane per (ray, rect, side); candidates go to LDS, the wave-uniform tail takes the minima
+// One lidar task: ray k = t / NR of robot `ridx` against rect j = t % NR (the other robots in index order, then the walls);
+// front / back minima over the rect's four sides, in registers.  The callers own the loop over lanes and the candidates' homes.
+template <class C>
+RR_HD void lidar_task(const Arena<C> &A, const SimParams<typename C::Real> &sp, int ridx, int t, typename C::Real &bf, typename C::Real &bb) {
+    using R = typename C::Real;
+    const int k = t / C::NR, j = t % C::NR;
+    int lst = 0;
+    V2<R> a, b; // ray start, end
+    if (k == 0) { // back-mid -> front-mid ; front = RIGHT side, back = LEFT side
+        Seg<R> fr = robot_side(A, ridx, 0), bk = robot_side(A, ridx, 2);
+        b = { (fr.a.x + fr.b.x) / (R)2, (fr.a.y + fr.b.y) / (R)2 };
+        a = { (bk.a.x + bk.b.x) / (R)2, (bk.a.y + bk.b.y) / (R)2 };
+    } else if (k == 1) { a = robot_corner(A, ridx, BL); b = robot_corner(A, ridx, TR); }
+    else { a = robot_corner(A, ridx, TL); b = robot_corner(A, ridx, BR); }
+    R mr, cr;
+    slope_yint<R>(a, b, mr, cr, lst);
+    bf = inf_<R>(); bb = inf_<R>();
+    const R hx = sp.W / (R)2, hy = sp.H / (R)2;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        Seg<R> side;
+        R ms, cs;
+        if (j < C::NR - 1) {
+            const int ro = j < ridx ? j : j + 1;
+            side = robot_side(A, ro, s);
+            ms = A.sm[ro][s]; cs = A.sc[ro][s];
+        } else { // rect_walls = FloatRect(0, W, 0, H) (RR_EnvBase.py:74): corner = centre + (+-W/2, +-H/2)
+            const int ca = side_a(s), cb = side_b(s);
+            side = { { hx + ((ca & 1) ? hx : -hx), hy + ((ca & 2) ? hy : -hy) },
+                     { hx + ((cb & 1) ? hx : -hx), hy + ((cb & 2) ? hy : -hy) } };
+            // get_slope_yint of the wall sides, constant: RIGHT (W,0)->(W,H) +inf/-inf; TOP (0,0)->(W,0) 0/0;
+            // LEFT (0,H)->(0,0) -inf/+inf; BOTTOM (W,H)->(0,H) -0.0 / H
+            ms = s == 0 ? inf_<R>() : s == 2 ? -inf_<R>() : s == 1 ? (R)0 : (R)-0.0;
+            cs = s == 0 ? -inf_<R>() : s == 2 ? inf_<R>() : s == 1 ? (R)0 : sp.H;
+        }
+        V2<R> I = intersect_mb<R>(ms, cs, side.a.x, mr, cr, a.x);
+        R de = dist<R>(I, b), ds = dist<R>(I, a);
+        if (de <= ds && de < bf) bf = de;
+        if (ds <= de && ds < bb) bb = ds;
+    }
+}
+// The scalar tail of one observation row, in two steps so that a caller can put a barrier between them.  observe_scalars: angles and
+// capped distances of robot `ridx` looking at ball `bidx`, turned round when `flip` (HAPPY looking at a negative ball, GRUMPY at a
+// positive one: RR_Observers.py:386-392), by value.  observe_row: the eleven values in the reference's order; the capped minima
+// (front / back of rays 0..2) come by value too, because a staged `row` may be the very array they were read from.
+template <typename R> struct ObsScalars { R bot_angle, ball_angle, ball_dist, goal_angle, goal_dist; };
+template <class C>
+RR_HD ObsScalars<typename C::Real> observe_scalars(const Arena<C> &A, const SimParams<typename C::Real> &sp, int ridx, int bidx, bool flip, int &st) {
+    using R = typename C::Real;
+    V2<R> rc = { A.p.rcx[ridx], A.p.rcy[ridx] }, bc = { A.p.bcx[bidx], A.p.bcy[bidx] };
+    V2<R> good = { sp.W, sp.H }, bad = { (R)0, (R)0 };
+    R ball_angle = angle_degrees<R>(rc, bc, st);
+    R ball_dist = py_min<R>(dist<R>(rc, bc), (R)150);
+    R goal_angle = angle_degrees<R>(rc, good, st);
+    R bot_angle = A.p.rrot[ridx];
+    R dbad = dist<R>(rc, bad), dgood = dist<R>(rc, good);
+    R goal_dist = (dgood <= dbad) ? py_min<R>(dgood, (R)390) : (R)-1 * py_min<R>(dbad, (R)390);
+    if (flip) {
+        goal_dist *= (R)-1;
+        ball_angle = py_mod<R>(ball_angle + (R)180, (R)360);
+        goal_angle = py_mod<R>(goal_angle + (R)180, (R)360);
+        bot_angle = py_mod<R>(bot_angle + (R)180, (R)360);
+    }
+    return { bot_angle, ball_angle, ball_dist, goal_angle, goal_dist };
+}
+template <typename R, typename O> RR_HD void observe_row(O *row, ObsScalars<R> s, R f0, R b0, R f1, R b1, R f2, R b2) {
+    row[0] = (O)s.bot_angle; row[1] = (O)s.ball_angle; row[2] = (O)s.ball_dist; row[3] = (O)s.goal_angle; row[4] = (O)s.goal_dist;
+    // lidar_front, front_l, front_r, back, back_l, back_r ; ray1 = (front_l, back_r), ray2 = (front_r, back_l)
+    row[5] = (O)f0; row[6] = (O)f1; row[7] = (O)f2; row[8] = (O)b0; row[9] = (O)b2; row[10] = (O)b1;
+}
+// lidar: one lane per (ray, rect); candidates go to LDS, the wave-uniform tail takes the minima
 template <class C, typename O>
-RR_HDN bool observe(Arena<C> &A, const SimParams<typename C::Real> &sp, int team, int ridx, int bidx, O *out, int &st) {
+RR_HD bool observe(Arena<C> &A, const SimParams<typename C::Real> &sp, int team, int ridx, int bidx, O *out, int &st) {
     using R = typename C::Real;
     if (ridx < 0) {
         if (team == 1 && C::NRH == 0) return false;
@@ -2764,41 +2719,8 @@ RR_HDN bool observe(Arena<C> &A, const SimParams<typename C::Real> &sp, int team
         RR_FOR_LANES(l) {
             const int t = base + l;
             if (t < NT) {
-                const int k = t / C::NR, j = t % C::NR;
-                int lst = 0;
-                V2<R> a, b; // ray start, end
-                if (k == 0) { // back-mid -> front-mid ; front = RIGHT side, back = LEFT side
-                    Seg<R> fr = robot_side(A, ridx, 0), bk = robot_side(A, ridx, 2);
-                    b = { (fr.a.x + fr.b.x) / (R)2, (fr.a.y + fr.b.y) / (R)2 };
-                    a = { (bk.a.x + bk.b.x) / (R)2, (bk.a.y + bk.b.y) / (R)2 };
-                } else if (k == 1) { a = robot_corner(A, ridx, BL); b = robot_corner(A, ridx, TR); }
-                else { a = robot_corner(A, ridx, TL); b = robot_corner(A, ridx, BR); }
-                R mr, cr;
-                slope_yint<R>(a, b, mr, cr, lst);
-                R bf = inf_<R>(), bb = inf_<R>();
-                const R hx = sp.W / (R)2, hy = sp.H / (R)2;
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    Seg<R> side;
-                    R ms, cs;
-                    if (j < C::NR - 1) {
-                        const int ro = j < ridx ? j : j + 1;
-                        side = robot_side(A, ro, s);
-                        ms = A.sm[ro][s]; cs = A.sc[ro][s];
-                    } else { // rect_walls = FloatRect(0, W, 0, H) (RR_EnvBase.py:74): corner = centre + (+-W/2, +-H/2)
-                        const int ca = side_a(s), cb = side_b(s);
-                        side = { { hx + ((ca & 1) ? hx : -hx), hy + ((ca & 2) ? hy : -hy) },
-                                 { hx + ((cb & 1) ? hx : -hx), hy + ((cb & 2) ? hy : -hy) } };
-                        // get_slope_yint of the wall sides, constant: RIGHT (W,0)->(W,H) +inf/-inf; TOP (0,0)->(W,0) 0/0;
-                        // LEFT (0,H)->(0,0) -inf/+inf; BOTTOM (W,H)->(0,H) -0.0 / H
-                        ms = s == 0 ? inf_<R>() : s == 2 ? -inf_<R>() : s == 1 ? (R)0 : (R)-0.0;
-                        cs = s == 0 ? -inf_<R>() : s == 2 ? inf_<R>() : s == 1 ? (R)0 : sp.H;
-                    }
-                    V2<R> I = intersect_mb<R>(ms, cs, side.a.x, mr, cr, a.x);
-                    R de = dist<R>(I, b), ds = dist<R>(I, a);
-                    if (de <= ds && de < bf) bf = de;
-                    if (ds <= de && ds < bb) bb = ds;
-                }
+                R bf, bb;
+                lidar_task(A, sp, ridx, t, bf, bb);
                 A.u.lidar[0][t] = bf;
                 A.u.lidar[1][t] = bb;
             }
@@ -2823,32 +2745,15 @@ RR_HDN bool observe(Arena<C> &A, const SimParams<typename C::Real> &sp, int team
     RR_SYNC();
     R lid[6]; // front, back per ray
     for (int k = 0; k < 6; k++) lid[k] = A.lid[k];
-    V2<R> rc = { A.p.rcx[ridx], A.p.rcy[ridx] }, bc = { A.p.bcx[bidx], A.p.bcy[bidx] };
-    V2<R> good = { sp.W, sp.H }, bad = { (R)0, (R)0 };
-    R ball_angle = angle_degrees<R>(rc, bc, st);
-    R ball_dist = py_min<R>(dist<R>(rc, bc), (R)150);
-    R goal_angle = angle_degrees<R>(rc, good, st);
-    R bot_angle = A.p.rrot[ridx];
-    R dbad = dist<R>(rc, bad), dgood = dist<R>(rc, good);
-    R goal_dist = (dgood <= dbad) ? py_min<R>(dgood, (R)390) : (R)-1 * py_min<R>(dbad, (R)390);
-    bool ball_neg = bidx >= C::NBP;
-    if ((team == 1 && ball_neg) || (team == -1 && !ball_neg)) {
-        goal_dist *= (R)-1;
-        ball_angle = py_mod<R>(ball_angle + (R)180, (R)360);
-        goal_angle = py_mod<R>(goal_angle + (R)180, (R)360);
-        bot_angle = py_mod<R>(bot_angle + (R)180, (R)360);
-    }
+    const bool ball_neg = bidx >= C::NBP;
+    const ObsScalars<R> sc = observe_scalars(A, sp, ridx, bidx, (team == 1 && ball_neg) || (team == -1 && !ball_neg), st);
     // The row leaves as ONE lane-strided run per arena (consecutive arenas of a wavefront are consecutive rows: 2 store
     // instructions per wavefront for eight 44-B rows instead of 11 single-lane ones): lane 0 parks the values in A.lid -- every
     // lane holds its copy of the six minima by now -- and the arena's lanes write them out side by side.
-    constexpr bool STAGED = RR_GPU && RR_OBS_STAGE && sizeof(A.lid) >= 11 * sizeof(O);
+    constexpr bool STAGED = RR_GPU && sizeof(A.lid) >= 11 * sizeof(O);
     if constexpr (STAGED) RR_SYNC();
     O *row = STAGED ? reinterpret_cast<O *>(&A.lid[0]) : out;
-    if (RR_IS_LANE0) {
-        row[0] = (O)bot_angle; row[1] = (O)ball_angle; row[2] = (O)ball_dist; row[3] = (O)goal_angle; row[4] = (O)goal_dist;
-        // lidar_front, front_l, front_r, back, back_l, back_r ; ray1 = (front_l, back_r), ray2 = (front_r, back_l)
-        row[5] = (O)lid[0]; row[6] = (O)lid[2]; row[7] = (O)lid[4]; row[8] = (O)lid[1]; row[9] = (O)lid[5]; row[10] = (O)lid[3];
-    }
+    if (RR_IS_LANE0) observe_row<R, O>(row, sc, lid[0], lid[1], lid[2], lid[3], lid[4], lid[5]);
     RR_SYNC();
     if constexpr (STAGED) {
         for (int base = 0; base < 11; base += C::VW) { RR_FOR_LANES(l) { if (base + l < 11) out[base + l] = row[base + l]; } }
@@ -2859,10 +2764,10 @@ RR_HDN bool observe(Arena<C> &A, const SimParams<typename C::Real> &sp, int team
 
 // Both teams' default observations (own robot 0, positive ball 0) in ONE pass: the 2 x 3 x NR (ray, rect) lidar tasks share
 // their rounds, and the two scalar tails (angles, distances) run side by side in lanes 0 and 1 instead of one after the
-// other.  Same per-task arithmetic as observe().  The second team's candidates live in per-sub-step ball scratch that is
-// dead by now (bfx..pfy, exc).
+// other.  The task and the tail are observe()'s own (lidar_task, observe_scalars, observe_row).  The second team's candidates live in per-sub-step
+// ball scratch that is dead by now (bfx..pfy, exc).
 template <class C, typename O>
-RR_HDN void observe_both(Arena<C> &A, const SimParams<typename C::Real> &sp, O *out_h, O *out_g, int &st) {
+RR_HD void observe_both(Arena<C> &A, const SimParams<typename C::Real> &sp, O *out_h, O *out_g, int &st) {
     using R = typename C::Real;
     static_assert(C::NRH > 0 && C::NRG > 0, "two teams");
     static_assert(6 * C::NR <= 4 * C::NB && 6 <= C::NB, "the second team's lidar scratch aliases bfx..pfy / exc");
@@ -2881,39 +2786,8 @@ RR_HDN void observe_both(Arena<C> &A, const SimParams<typename C::Real> &sp, O *
             const int t2 = base + l;
             if (t2 < 2 * NT1) {
                 const int tm = t2 / NT1, t = t2 % NT1, ridx = tm == 0 ? 0 : C::NRH;
-                const int k = t / C::NR, j = t % C::NR;
-                int lst = 0;
-                V2<R> a, b; // ray start, end
-                if (k == 0) { // back-mid -> front-mid ; front = RIGHT side, back = LEFT side
-                    Seg<R> fr = robot_side(A, ridx, 0), bk = robot_side(A, ridx, 2);
-                    b = { (fr.a.x + fr.b.x) / (R)2, (fr.a.y + fr.b.y) / (R)2 };
-                    a = { (bk.a.x + bk.b.x) / (R)2, (bk.a.y + bk.b.y) / (R)2 };
-                } else if (k == 1) { a = robot_corner(A, ridx, BL); b = robot_corner(A, ridx, TR); }
-                else { a = robot_corner(A, ridx, TL); b = robot_corner(A, ridx, BR); }
-                R mr, cr;
-                slope_yint<R>(a, b, mr, cr, lst);
-                R bf = inf_<R>(), bb = inf_<R>();
-                const R hx = sp.W / (R)2, hy = sp.H / (R)2;
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    Seg<R> side;
-                    R ms, cs;
-                    if (j < C::NR - 1) {
-                        const int ro = j < ridx ? j : j + 1;
-                        side = robot_side(A, ro, s);
-                        ms = A.sm[ro][s]; cs = A.sc[ro][s];
-                    } else { // rect_walls = FloatRect(0, W, 0, H) (RR_EnvBase.py:74), see observe()
-                        const int ca = side_a(s), cb = side_b(s);
-                        side = { { hx + ((ca & 1) ? hx : -hx), hy + ((ca & 2) ? hy : -hy) },
-                                 { hx + ((cb & 1) ? hx : -hx), hy + ((cb & 2) ? hy : -hy) } };
-                        ms = s == 0 ? inf_<R>() : s == 2 ? -inf_<R>() : s == 1 ? (R)0 : (R)-0.0;
-                        cs = s == 0 ? -inf_<R>() : s == 2 ? inf_<R>() : s == 1 ? (R)0 : sp.H;
-                    }
-                    V2<R> I = intersect_mb<R>(ms, cs, side.a.x, mr, cr, a.x);
-                    R de = dist<R>(I, b), ds = dist<R>(I, a);
-                    if (de <= ds && de < bf) bf = de;
-                    if (ds <= de && ds < bb) bb = ds;
-                }
+                R bf, bb;
+                lidar_task(A, sp, ridx, t, bf, bb);
                 cand(tm, 0)[t] = bf;
                 cand(tm, 1)[t] = bb;
             }
@@ -2938,7 +2812,7 @@ RR_HDN void observe_both(Arena<C> &A, const SimParams<typename C::Real> &sp, O *
     }
     RR_SYNC();
     uint64_t any_div0 = 0;
-    constexpr bool STAGED = RR_GPU && RR_OBS_STAGE && sizeof(A.lid) >= 11 * sizeof(O) && sizeof(A.exc) >= 11 * sizeof(O);
+    constexpr bool STAGED = RR_GPU && sizeof(A.lid) >= 11 * sizeof(O) && sizeof(A.exc) >= 11 * sizeof(O);
     RR_FOR_LANES(l) { // the scalar tails of the two teams, side by side
         int lst = 0;
         if (l < 2) {
@@ -2946,25 +2820,11 @@ RR_HDN void observe_both(Arena<C> &A, const SimParams<typename C::Real> &sp, O *
             O *out = l == 0 ? out_h : out_g;
             R lid[6]; // (by value: the team's staged output row reuses this very array below)
             for (int k = 0; k < 6; k++) lid[k] = lids(l)[k];
-            V2<R> rc = { A.p.rcx[ridx], A.p.rcy[ridx] }, bc = { A.p.bcx[0], A.p.bcy[0] };
-            V2<R> good = { sp.W, sp.H }, bad = { (R)0, (R)0 };
-            R ball_angle = angle_degrees<R>(rc, bc, lst);
-            R ball_dist = py_min<R>(dist<R>(rc, bc), (R)150);
-            R goal_angle = angle_degrees<R>(rc, good, lst);
-            R bot_angle = A.p.rrot[ridx];
-            R dbad = dist<R>(rc, bad), dgood = dist<R>(rc, good);
-            R goal_dist = (dgood <= dbad) ? py_min<R>(dgood, (R)390) : (R)-1 * py_min<R>(dbad, (R)390);
-            if (l == 1) { // GRUMPY looking at a positive ball (RR_Observers.py:386-392)
-                goal_dist *= (R)-1;
-                ball_angle = py_mod<R>(ball_angle + (R)180, (R)360);
-                goal_angle = py_mod<R>(goal_angle + (R)180, (R)360);
-                bot_angle = py_mod<R>(bot_angle + (R)180, (R)360);
-            }
+            const ObsScalars<R> sc = observe_scalars(A, sp, ridx, 0, l == 1, lst); // (GRUMPY looks at a positive ball)
             // staged (see observe()): each team's row is parked in the array its minima came from -- A.lid / A.exc, read into
             // registers above by this very lane -- and leaves as lane-strided runs below
             O *row = STAGED ? reinterpret_cast<O *>(lids(l)) : out;
-            row[0] = (O)bot_angle; row[1] = (O)ball_angle; row[2] = (O)ball_dist; row[3] = (O)goal_angle; row[4] = (O)goal_dist;
-            row[5] = (O)lid[0]; row[6] = (O)lid[2]; row[7] = (O)lid[4]; row[8] = (O)lid[1]; row[9] = (O)lid[5]; row[10] = (O)lid[3];
+            observe_row<R, O>(row, sc, lid[0], lid[1], lid[2], lid[3], lid[4], lid[5]);
         }
         RR_VOTE(any_div0, l, (lst & ST_DIV0) != 0);
     }
@@ -2988,9 +2848,7 @@ template <class C> RR_HD void derive(Arena<C> &A, const SimParams<typename C::Re
     using R = typename C::Real;
     RR_FOR_LANES(l) {
         if (l < C::NR) {
-#ifndef RR_REL_IN_RECORD
-            corners_for<R>(A.p.rrot[l], (R)10, (R)20, sp.rob_cdist, RR_REL(A)[l]);
-#endif
+            corners_for<R>(A.p.rrot[l], (R)10, (R)20, sp.rob_cdist, A.rel[l]);
             A.irot[l] = (R)NAN; // inner-square offsets are built lazily by the first narrow phase that needs them
         }
     }
@@ -3050,7 +2908,7 @@ template <class C> RR_HD IRect robot_irect(const Arena<C> &A, int r) { return ir
 template <class C> RR_HD IRect ball_irect(const Arena<C> &A, int b) { return irect(A.p.bl[b], A.p.bt[b], A.p.brt[b], A.p.bb[b]); }
 
 template <class C>
-RR_HDN void reset_arena(Arena<C> &A, const SimParams<typename C::Real> &sp, uint64_t arena_gid, uint64_t episode, int &st) {
+RR_HD void reset_arena(Arena<C> &A, const SimParams<typename C::Real> &sp, uint64_t arena_gid, uint64_t episode, int &st) {
     using R = typename C::Real;
     Rng g = { sp.seed, arena_gid, episode, 0 };
     const int MAX_TRY = 4096;
@@ -3324,11 +3182,7 @@ RR_HD void step_arena(Arena<C> &A, const SimParams<typename C::Real> &sp, uint64
     int icm = 0;  // parity build: 1 while the scratch rect is implicitly on the last ball (carry_quiet_sweep); 0: A.p.ic holds it
     // (what the packed word holds; and not under the F32State policy: the record is rounded to fp32 between two steps, so the island a
     // step ended with is not bit for bit the one the next step would find)
-#ifdef RR_NO_FZP // A/B builds only
-    constexpr bool FZP = false;
-#else
     constexpr bool FZP = C::NR <= 4 && C::NB <= 8 && !C::MIXED;
-#endif
     bool resumed = false;
     RR_T0();
     if constexpr (BUDGET) {
@@ -3488,7 +3342,6 @@ RR_HD void step_arena(Arena<C> &A, const SimParams<typename C::Real> &sp, uint64
                 // drifting edge bits, which is most of what a trained or chase policy runs into on preset T)
                 if (island_ok) {
                     fz = hit;
-#ifndef RR_NO_NEIGHBOURS // (A/B builds only)
                     if (hit.r) {
                         const uint32_t nb_ = resting_neighbours(A, hit, chg_b);
 #if RR_CARRY
@@ -3497,7 +3350,6 @@ RR_HD void step_arena(Arena<C> &A, const SimParams<typename C::Real> &sp, uint64
                         fz.b |= nb_;
 #endif
                     }
-#endif
                     RR_TRACE("E freeze robots %x balls %x (hit %x) after sub-step %d\n", fz.r, fz.b, hit.b, f);
                     fz_bits = fz_pack_bits(n_sub, st_sub);
                 } else {

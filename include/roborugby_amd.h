@@ -230,6 +230,34 @@ int rr_hive_observe_f64(rr_env *env, uint32_t robot_mask, int32_t kind, int32_t 
  * arena is parked returns -1 and changes nothing -- no copies were kept when those steps began (see rr_set_reward_program). */
 int rr_track_prior_step(rr_env *env, int32_t on, void *stream);
 
+/* Training the hive in the full game: the transition of every hive robot over the step that was just taken, in ONE launch.  Call order:
+ * rr_track_prior_step(env, 1) once; then per step rr_hive_observe (assign, obs) -> rr_step* (status, done) -> this.
+ * assign [N,NR] i32:  what rr_hive_observe wrote BEFORE the step.  status [N] i32, done [N] u8: the step's.
+ * Row (a, r) is VALID when r is in robot_mask, 0 <= assign[a,r] < NB (any other value, garbage included, makes the row invalid and is
+ * never used as an index), the step's status has none of RR_STATUS_WAS_RESET / NOT_READY / STEP_AFTER_DONE, and the ball is still in
+ * play (opt-in goal scoring: a ball consumed during this step ends the pairing without a transition).  For a valid row
+ *   next_obs [N,NR,11]: what rr_observe_kind(kind, team of r, r, assign[a,r]) returns on the record after the step -- the ball is held,
+ *                       not re-assigned, even if it now lies in a goal;
+ *   reward [N,NR]:      the reference has no per-robot reward; this is SimpleDuel3's three keepers restricted to the pair, summed in the
+ *                       handle's arithmetic type from 0 in this order: (1) NaughtyBots: -0.005 if status bit 16 + r is set;
+ *                       (2) ChasePosBall: (dist(prior_r, ball_now) - dist(robot_now, ball_now)) * mult_robot, prior_r the robot's
+ *                       on_step_begin copy, ball_now the ball's centre after the step in both distances; (3) PushPosBallsToGoal:
+ *                       sgn * (dist((0,0), ball_now) - dist((0,0), ball_prior)) * mult_ball, ball_prior the ball's on_step_begin copy,
+ *                       sgn = (r happy ? +1 : -1) * (ball positive ? +1 : -1) -- negative for exactly the pairs whose observation is
+ *                       turned round.  dist is MyUtils.distance as the reference evaluates it, ((bx-ax)**2 + (by-ay)**2)**.5 with
+ *                       both powers through pow().  With one robot per team and positive ball 0 the sum is the team's reward: the
+ *                       reference's own bit for bit where pow is the host libm's, rr_step's within a few 1e-11 on the device;
+ *   terminal [N,NR] u8: done[a].
+ * Invalid rows: next_obs 0, reward 0, terminal 0, valid [N,NR] u8 0.  Every output element is written on every call.
+ * Returns -1 (message in rr_last_error, nothing launched): null handle / pointer; empty mask or a mask bit >= NR; kind not 0 or 1;
+ * prior-step tracking off; a handle that has (had) a step budget -- a parked arena's pre-step assignment is overwritten by the next
+ * rr_hive_observe before its step completes.  Read-only on the records and the snapshot.  rr_hive_transition_f64 refuses RR_DTYPE_F32
+ * like rr_hive_observe_f64. */
+int rr_hive_transition(rr_env *env, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
+                       float *next_obs, float *reward, uint8_t *terminal, uint8_t *valid, void *stream);
+int rr_hive_transition_f64(rr_env *env, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
+                           double *next_obs, double *reward, uint8_t *terminal, uint8_t *valid, void *stream);
+
 /* Opt-in goal scoring -- an EXTENSION: on the reference's live path the goals never score (Goal.track_balls / update_score are
  * only reached from the never-called GameEnv.__old_step, RR_EnvBase.py:458-520; RR_Goal.py:80 calls a property as a function),
  * so there is no reference behaviour to match; this is the mechanism of RR_Goal.py:54-91 + the commented block at

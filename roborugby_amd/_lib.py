@@ -61,6 +61,8 @@ SYMBOLS = {
     "rr_observe_kind_f64": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp]),
     "rr_hive_observe": (C.c_int, [_vp, C.c_uint32, C.c_int32, _vp, _vp, _vp]),
     "rr_hive_observe_f64": (C.c_int, [_vp, C.c_uint32, C.c_int32, _vp, _vp, _vp]),
+    "rr_hive_transition": (C.c_int, [_vp, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rr_hive_transition_f64": (C.c_int, [_vp, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rr_track_prior_step": (C.c_int, [_vp, C.c_int32, _vp]),
     "rr_set_goal_scoring": (C.c_int, [_vp, C.c_int32, _vp]),
     "rr_goal_scores": (C.c_int, [_vp, _vp, _vp]),

@@ -137,4 +137,89 @@ RR_HD void hive_observe(Arena<C> &A, const Rec<C> &q, const SimParams<typename C
     }
 }
 
+// ---- training the hive in the full game: the transition of every hive robot over the step that was just taken.
+//
+// The reference has no per-robot reward; this is the project's definition: for robot r going for ball b, SimpleDuel3's three keepers
+// restricted to that pair.  Starting from (R)0, in this order:
+//   1. NaughtyBots:        -0.005 if bit 16 + r of the step's status is set;
+//   2. ChasePosBall:       (dist(prior_r, ball_now) - dist(robot_now, ball_now)) * mult_robot -- prior_r the robot's on_step_begin copy
+//                          (xs[3 r], xs[3 r + 1]), ball_now the ball's centre AFTER the step in both distances, as the reference has it;
+//   3. PushPosBallsToGoal: sgn * (dist((0,0), ball_now) - dist((0,0), ball_prior)) * mult_ball -- ball_prior the snapshot's ball copy
+//                          (xs_ball<C>(b)); sgn = (r happy ? +1 : -1) * (b positive ? +1 : -1): negative exactly for the pairs whose view
+//                          observe() turns round (`flip`), so a policy trained in preset T sees one consistent game.
+// `dist` here is ref_dist below -- MyUtils.distance as the reference evaluates it, ((bx - ax) ** 2 + (by - ay) ** 2) ** .5 with both
+// powers through libm's pow -- NOT the step kernel's dist<R> (x * x and sqrt, a last-bit difference on about one distance in a thousand).
+// With one robot per team and positive ball 0 the sum is then the REFERENCE's team reward bit for bit on the host, on every recorded step
+// of presets T and D (tests/test_hive_transition_emulated.py; with dist<R> 6 of T's 4,564 steps are off by up to 2.7e-11).  On the device
+// pow is the device library's: equal to k_step's reward and to the reference's within a few 1e-11 (tests/test_gpu_hive_transition.py: 1e-9).
+// The cost is five pow-based distances per hive robot and launch, next to an 11-value lidar observation.
+//
+// A row is VALID when its robot is in robot_mask, 0 <= assign[r] < NB (any other value is never used as an index), the step's status
+// has none of WAS_RESET / NOT_READY / STEP_AFTER_DONE, and the ball is still in play (with the opt-in goal scoring a ball consumed
+// during this step ends the pairing without a transition).  next_obs of a valid row is the robot's observation of THE SAME ball on the
+// record after the step -- the ball is held, not re-assigned, even if it now lies in a goal.  Invalid rows are all 0.
+// assign [NR], next_obs [NR][11], reward / terminal / valid [NR] of this arena; xs the arena's on_step_begin snapshot (rr_extras.hpp).
+// Kind as in hive_observe (kind OBS_V2: A must be derive()d).  Read-only on A's persistent part, q and xs; no atomics.
+RR_HD double m_pow(double x, double y) { return ::pow(x, y); }
+RR_HD float m_pow(float x, float y) { return ::powf(x, y); }
+template <typename R> RR_HD R ref_dist(V2<R> a, V2<R> b) { // MyUtils.py:40-41, `**` as CPython evaluates it
+    return m_pow(m_pow(b.x - a.x, (R)2) + m_pow(b.y - a.y, (R)2), (R).5);
+}
+template <class C, typename O, int KIND>
+RR_HD void hive_transition(Arena<C> &A, const Rec<C> &q, const SimParams<typename C::Real> &sp, const typename C::Real *xs,
+                            uint32_t robot_mask, const int32_t *assign, int32_t status, uint8_t done, O *next_obs, O *reward,
+                            uint8_t *terminal, uint8_t *valid) {
+    using R = typename C::Real;
+    static_assert(C::NB <= 16 && C::NR <= 16, "a ball index per robot in four bits, a NaughtyBots bit per robot in status bits 16..31");
+    const bool stepped = !(status & (ST_WAS_RESET | ST_NOT_READY | ST_STEP_AFTER_DONE));
+    uint32_t ok = 0;     // bit r = row r is valid; uniform over the arena's lanes (every lane reads the arena's NR words)
+    uint64_t which = 0;  // its ball in bits 4r .. 4r+3
+    for (int r = 0; r < C::NR; r++) {
+        const int32_t b = assign[r];
+        if (stepped && ((robot_mask >> r) & 1u) && b >= 0 && b < C::NB && ball_in_play(A, b)) {
+            ok |= 1u << r;
+            which |= (uint64_t)b << (4 * r);
+        }
+    }
+    // rewards: one lane per robot, the snapshot words and the record's centres straight from HBM
+    RR_FOR_LANES(l) {
+        if (l < C::NR) {
+            R rw = (R)0;
+            const bool v = (ok >> l) & 1u;
+            if (v) {
+                const int b = (int)((which >> (4 * l)) & 15u);
+                if (((uint32_t)status >> (16 + l)) & 1u) rw -= (R).005;
+                const V2<R> bc = { q.bcx(b), q.bcy(b) }, rc = { q.rcx(l), q.rcy(l) }, pc = { xs[3 * l], xs[3 * l + 1] };
+                rw += (ref_dist<R>(pc, bc) - ref_dist<R>(rc, bc)) * sp.mult_robot;
+                const V2<R> o = { (R)0, (R)0 }, pb = { xs[xs_ball<C>(b)], xs[xs_ball<C>(b) + 1] };
+                const R push = (ref_dist<R>(o, bc) - ref_dist<R>(o, pb)) * sp.mult_ball;
+                const bool flip = (l < C::NRH) != (b < C::NBP);
+                if (flip) rw -= push; else rw += push;
+            }
+            reward[l] = (O)rw;
+            terminal[l] = v ? done : (uint8_t)0;
+            valid[l] = v ? 1 : 0;
+        }
+    }
+    if constexpr (KIND == OBS_V2) {
+#pragma unroll 1
+        for (int r = 0; r < C::NR; r++) { // (one copy of observe(), as in hive_observe)
+            if ((ok >> r) & 1u) {
+                int st = 0;
+                observe<C, O>(A, sp, r < C::NRH ? 1 : -1, r, (int)((which >> (4 * r)) & 15u), next_obs + 11 * r, st);
+            } else {
+                for (int base = 0; base < 11; base += C::VW) { RR_FOR_LANES(l) { if (base + l < 11) next_obs[11 * r + base + l] = (O)0; } }
+            }
+        }
+    } else {
+        RR_FOR_LANES(l) {
+            if (l < C::NR) {
+                O *o = next_obs + 11 * l;
+                if ((ok >> l) & 1u) observe_kind<C, O>(q, sp, OBS_V1, l < C::NRH ? 1 : -1, l, (int)((which >> (4 * l)) & 15u), o);
+                else for (int k = 0; k < 11; k++) o[k] = (O)0;
+            }
+        }
+    }
+}
+
 } // namespace rr

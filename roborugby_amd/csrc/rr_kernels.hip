@@ -334,6 +334,26 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
     Rec<C> q = { rec };
     hive_observe<C, O, KIND>(A, q, sp, robot_mask, assign + (size_t)arena * C::NR, obs + (size_t)arena * C::NR * 11);
 }
+// Training the hive (rr_hive.hpp: hive_transition): after a step, every hive robot's next observation of the ball it was going for, its
+// reward, terminal and valid flag, in one launch next to k_hive -- same geometry, same launch bounds, same loads.  Read-only on the
+// records and on the on_step_begin snapshot `xs` (rr_track_prior_step keeps it); no atomics, every output element is written.
+template <class C, typename O, int KIND>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void k_hive_transition(
+    SimParams<typename C::Real> sp, const typename C::Store *recs, const int32_t *irecs, int n, const typename C::Real *xs, uint32_t robot_mask,
+    const int32_t *assign, const int32_t *status, const uint8_t *done, O *next_obs, O *reward, uint8_t *terminal, uint8_t *valid) {
+    __shared__ Arena<C> lds[arenas_per_block<C>()];
+    const int wave = threadIdx.x / C::VW; // virtual wave = arena slot in this workgroup
+    const int arena = blockIdx.x * arenas_per_block<C>() + wave;
+    if (arena >= n || wave >= arenas_per_block<C>()) return;
+    Arena<C> &A = lds[wave];
+    const typename C::Store *rec = recs + (size_t)arena * Arena<C>::P_STRIDE;
+    load_record(A, rec, irecs + (size_t)arena * Arena<C>::I_STRIDE);
+    if (KIND == OBS_V2) derive(A, sp);
+    Rec<C> q = { rec };
+    const size_t row = (size_t)arena * C::NR;
+    hive_transition<C, O, KIND>(A, q, sp, xs + (size_t)arena * xs_stride<C>(), robot_mask, assign + row, status[arena], done[arena],
+                                next_obs + row * 11, reward + row, terminal + row, valid + row);
+}
 
 // Scripted on-device policy of the contact-rich workload ("turn toward ball_angle, else forward, 10 %
 // random"): robot 0 of every arena chases its ball from the arena's own observation row, the other robots act at random.
@@ -848,6 +868,26 @@ static int hive_observe_impl(rr_env *e, uint32_t robot_mask, int32_t kind, int32
         return 0;
     }, "rr_hive_observe_f64: handle was created with RR_DTYPE_F32");
 }
+template <typename O>
+static int hive_transition_impl(rr_env *e, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
+                                O *next_obs, O *reward, uint8_t *terminal, uint8_t *valid, void *stream) {
+    if (!e || !assign || !status || !done || !next_obs || !reward || !terminal || !valid) return fail(-1, "rr_hive_transition: null argument");
+    if (kind != OBS_V2 && kind != OBS_V1)
+        return fail(-1, "rr_hive_transition: observer kind must be 0 (SingleBall_6wayLidar_v2) or 1 (SingleBall_6wayLidar)");
+    const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy;
+    if (!robot_mask) return fail(-1, "rr_hive_transition: empty robot mask");
+    if (nr < 32 && (robot_mask >> nr)) return fail(-1, "rr_hive_transition: robot mask has a bit at or above the number of robots");
+    if (!(e->track_prior && e->xs))
+        return fail(-1, "rr_hive_transition: needs rr_track_prior_step(env, 1) before the step it looks back on (the rewards read the on_step_begin copies)");
+    if (e->park) // (a parked arena's pre-step assignment is overwritten by the next rr_hive_observe before its step completes)
+        return fail(-1, "rr_hive_transition: not on a handle with a step budget (arenas may be parked mid-step)");
+    return on_handle<O>(e, "rr_hive_transition", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        v.per_wave(kind == OBS_V2 ? k_hive_transition<C, O, OBS_V2> : k_hive_transition<C, O, OBS_V1>, v.sp(), v.recs(), v.irecs(), v.n(), v.xs(),
+                   robot_mask, assign, status, done, next_obs, reward, terminal, valid);
+        return 0;
+    }, "rr_hive_transition_f64: handle was created with RR_DTYPE_F32");
+}
 } // extern "C++"
 int rr_observe_kind(rr_env *e, int32_t kind, int32_t team, int32_t ridx, int32_t bidx, float *obs, int32_t out_dim, void *stream) {
     return observe_kind_impl<float>(e, kind, team, ridx, bidx, obs, out_dim, stream);
@@ -862,6 +902,14 @@ int rr_hive_observe(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assig
 }
 int rr_hive_observe_f64(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, double *obs, void *stream) {
     return hive_observe_impl<double>(e, robot_mask, kind, assign, obs, stream);
+}
+int rr_hive_transition(rr_env *e, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
+                       float *next_obs, float *reward, uint8_t *terminal, uint8_t *valid, void *stream) {
+    return hive_transition_impl<float>(e, robot_mask, kind, assign, status, done, next_obs, reward, terminal, valid, stream);
+}
+int rr_hive_transition_f64(rr_env *e, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
+                           double *next_obs, double *reward, uint8_t *terminal, uint8_t *valid, void *stream) {
+    return hive_transition_impl<double>(e, robot_mask, kind, assign, status, done, next_obs, reward, terminal, valid, stream);
 }
 
 int rr_set_state(rr_env *e, const double *robots, const int32_t *ri, const double *balls, const int32_t *step, void *stream) {

@@ -644,11 +644,92 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
     return res
 
 
+def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og_twitchy", resume=None, checkpoint=None,
+               updates_per_step=4, device="cuda:0", seed=0, dtype="f64", batch_size=None, mem_size=None, replay_vector_steps=32,
+               target_sync_vector_steps=64, eps_dec=.999997, eps_end=0.2, epsilon=None, learn=True, log_every=50, out=None,
+               observer=None):
+    """Training the hive mind IN the full game: one agent, one transition per hive robot and step.  Per vector step, serial on one
+    stream: hive.epsilon = agent.epsilon -> `opponents` ('og_twitchy' or None = stand still) fill the other robots' thrust columns ->
+    hive.act -> env.step_thrust -> hive.store (rr_hive_transition + one rr_dqn_store over the N * NR rows) -> updates_per_step x
+    agent.learn().  The reward of a row is the per-robot reward of include/roborugby_amd.h (rr_hive_transition), its next state the
+    robot's view of the ball it was going for; rows without a ball / of re-placed arenas are no transitions.
+    robots: the hive (None: the happy team).  resume: a checkpoint of train() or of this function -- the AGENT is taken from it (a policy
+    trained in preset T is fine-tuned in G), the env starts fresh.  The checkpoint written is one play_hive reads.  Returns a dict like
+    train()'s: throughput (HIP events around the loop), transitions stored, valid share, epsilon, mean per-robot reward."""
+    import roborugby_amd as rr
+    from .players import Hive, og_twitchy
+    if opponents not in ("og_twitchy", None):
+        raise ValueError("opponents: 'og_twitchy' or None")
+    env = rr.BatchedRoboRugbyEnv(num_envs, preset=preset, device=device, seed=seed, dtype=dtype, action_mode="thrust")
+    env.track_prior_step()  # the rewards look back on every robot's and ball's position at the step's begin
+    p = env.preset
+    members = tuple(range(p.nr_happy)) if robots is None else tuple(sorted({int(r) for r in robots}))
+    rows = num_envs * len(members)
+    B = int(batch_size or min(32768, max(64, rows // 2 // 64 * 64)))
+    agent = BatchedDQNAgent(input_dims=11, batch_size=B, n_actions=8, device=device, seed=seed,
+                            max_mem_size=mem_size or max(500000, replay_vector_steps * rows),
+                            target_update_freq=max(100000, target_sync_vector_steps * rows), eps_dec=eps_dec, eps_end=eps_end)
+    if resume:
+        agent.load_state_dict(torch.load(resume, map_location=device)["agent"])
+    if epsilon is not None:
+        agent.epsilon = float(epsilon)
+    hive = Hive(env, agent, robots=members, epsilon=agent.epsilon, seed=seed, observer=observer)
+    gen = torch.Generator(device=env.device)
+    gen.manual_seed(seed + 1)
+    env.reset()
+    thrust = torch.zeros(num_envs, 2 * p.nr, dtype=torch.float32, device=env.device)
+    valid_rows = torch.zeros((), dtype=torch.int64, device=env.device)
+    reward_sum = torch.zeros((), dtype=torch.float64, device=env.device)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for i in range(steps):
+        hive.epsilon = agent.epsilon
+        if opponents and len(members) < p.nr:
+            thrust.copy_(og_twitchy(num_envs, p.nr, generator=gen, device=env.device))  # (the hive's columns are overwritten by act)
+        hive.act(out=thrust)
+        _, _, done, info = env.step_thrust(thrust)
+        if learn:
+            hive.store(agent, done, info.status)
+            for _ in range(updates_per_step):
+                agent.learn()
+        else:
+            hive.transition(done, info.status)
+        valid_rows += hive._valid.sum()
+        reward_sum += hive._reward.sum(dtype=torch.float64)  # (invalid rows carry 0)
+        if log_every and (i + 1) % log_every == 0:
+            torch.cuda.synchronize(env.device)
+            print(f"step {i + 1} epsilon {agent.epsilon:.6f} stored {agent.mem_cntr} updates {agent.updates} mean-robot-reward "
+                  f"{float(reward_sum) / max(int(valid_rows), 1):.4f} loss "
+                  f"{float(agent.last_loss) if agent.last_loss is not None else float('nan'):.4f}", flush=True)
+    t1.record()
+    torch.cuda.synchronize(env.device)
+    secs = t0.elapsed_time(t1) / 1e3
+    if checkpoint:
+        os.makedirs(os.path.dirname(os.path.abspath(checkpoint)), exist_ok=True)
+        torch.save(dict(agent=agent.state_dict(), mode="train_hive", preset=preset, hive_robots=list(members)), checkpoint)
+    n_valid = int(valid_rows.item())
+    res = dict(mode="train_hive", preset=preset, dtype=dtype, num_envs=num_envs, steps=steps, hive_robots=list(members), opponents=opponents,
+               env_steps_per_sec=num_envs * steps / secs, seconds=secs, ms_per_vector_step=1e3 * secs / max(steps, 1),
+               transitions=int(agent.mem_cntr) if learn else 0, valid_rows=n_valid, valid_share=n_valid / max(rows * steps, 1),
+               epsilon=agent.epsilon, mean_robot_reward=float(reward_sum.item()) / max(n_valid, 1), learn_calls=agent.updates,
+               updates_per_step=updates_per_step if learn else 0, batch_size=B, replay_transitions=agent.mem_size,
+               loss=float(agent.last_loss) if agent.last_loss is not None else None, fused_learn_step=bool(agent.fused),
+               resumed_from=resume)
+    hive.close()
+    agent.close()
+    env.close()
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)) or ".", exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-envs", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=300)
-    ap.add_argument("--preset", default="T")
+    ap.add_argument("--preset", default=None, help="T (default), or any preset name; --train-hive / --play-hive: G")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--checkpoint", default=None)
@@ -666,11 +747,19 @@ def main():
     ap.add_argument("--budget", type=int, default=0, help="step_budget_clocks of the env (the budgeted step; 0 = synchronous)")
     ap.add_argument("--play-hive", default=None, metavar="CHECKPOINT",
                     help="no training: the checkpoint's policy plays preset G as the happy team's hive mind against OG_Twitchy (--num-envs, --steps)")
+    ap.add_argument("--train-hive", action="store_true",
+                    help="train the hive mind in the full game (preset G): one transition per hive robot and step; --resume takes the agent of "
+                         "any checkpoint, e.g. one trained in preset T (--num-envs, --steps, --checkpoint, --updates-per-step, --batch-size)")
     a = ap.parse_args()
     if a.play_hive:
-        print(json.dumps(play_hive(a.play_hive, a.num_envs, a.steps, a.device, a.seed)))
+        print(json.dumps(play_hive(a.play_hive, a.num_envs, a.steps, a.device, a.seed, preset=a.preset or "G")))
         return
-    res = train(a.num_envs, a.steps, a.preset, a.device, a.seed, a.checkpoint, a.resume, learn=not a.no_learn,
+    if a.train_hive:
+        print(json.dumps(train_hive(a.num_envs, a.steps, a.preset or "G", resume=a.resume, checkpoint=a.checkpoint,
+                                    updates_per_step=a.updates_per_step, device=a.device, seed=a.seed, batch_size=a.batch_size,
+                                    eps_dec=a.eps_dec, learn=not a.no_learn, log_every=a.log_every, out=a.out)))
+        return
+    res = train(a.num_envs, a.steps, a.preset or "T", a.device, a.seed, a.checkpoint, a.resume, learn=not a.no_learn,
                 updates_per_step=a.updates_per_step, batch_size=a.batch_size, eps_dec=a.eps_dec, eval_every=a.eval_every,
                 eval_envs=a.eval_envs, log_every=a.log_every, out=a.out, overlap_learn=not a.no_overlap,
                 step_budget_clocks=a.budget, fused=False if a.no_fused else None)

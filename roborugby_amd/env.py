@@ -432,6 +432,41 @@ class BatchedRoboRugbyEnv:
         _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(obs), self._stream()), "rr_hive_observe", self._lib)
         return assign, obs
 
+    def track_prior_step(self, on=True):
+        """rr_track_prior_step: every step from now on first snapshots what the sprites' on_step_begin copies (robot and ball centres at
+        the step's begin).  observer='AllCoords_WithPrior' switches it on by itself; hive_transition needs it on BEFORE the step it
+        looks back on."""
+        _lib.check(self._lib.rr_track_prior_step(self._h, int(bool(on)), self._stream()), "rr_track_prior_step", self._lib)
+
+    def hive_transition(self, assign, status, done, robot_mask=None, observer=None, f64=False, out=None):
+        """Training the hive in the full game: the transition of every hive robot over the step that was just taken, in one launch
+        (rr_hive_transition) -> (next_obs [N,NR,11], reward [N,NR], terminal uint8 [N,NR], valid uint8 [N,NR]).
+        assign: what hive_observe returned BEFORE the step; status, done: the step's (info.status, done).  A row is valid when its robot
+        is in the mask, was given a ball, the arena really stepped (not re-placed, not STEP_AFTER_DONE) and the ball is still in play;
+        then next_obs is the robot's observation of THE SAME ball after the step, reward the per-robot reward defined in
+        include/roborugby_amd.h and terminal = done.  Invalid rows are 0.  Needs track_prior_step() before the step; refuses a handle with
+        a step budget.  robot_mask / observer / f64 as in hive_observe; out: the four tensors to reuse."""
+        p, N = self.preset, self.num_envs
+        mask = (1 << p.nr_happy) - 1 if robot_mask is None else int(robot_mask)
+        kind = (self.obs_kind if self.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
+        od = torch.float64 if f64 else torch.float32
+        if out is None:
+            out = (self._new((N, p.nr, 11), od), self._new((N, p.nr), od), self._new((N, p.nr), torch.uint8), self._new((N, p.nr), torch.uint8))
+        next_obs, reward, terminal, valid = out
+        assert assign.dtype == torch.int32 and assign.is_contiguous() and assign.numel() == N * p.nr and assign.device == self.device
+        assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == N and status.device == self.device
+        done = done.view(torch.uint8) if done.dtype == torch.bool else done
+        assert done.dtype == torch.uint8 and done.is_contiguous() and done.numel() == N and done.device == self.device
+        assert next_obs.dtype == od and next_obs.is_contiguous() and next_obs.numel() >= N * p.nr * 11
+        assert reward.dtype == od and reward.is_contiguous() and reward.numel() >= N * p.nr
+        assert all(t.dtype in (torch.uint8, torch.bool) and t.is_contiguous() and t.numel() >= N * p.nr for t in (terminal, valid))
+        if mask < 0 or mask > 0xFFFFFFFF:
+            raise ValueError("robot_mask: one bit per robot")
+        fn = self._lib.rr_hive_transition_f64 if f64 else self._lib.rr_hive_transition
+        _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(status), _ptr(done), _ptr(next_obs), _ptr(reward), _ptr(terminal), _ptr(valid),
+                      self._stream()), "rr_hive_transition", self._lib)
+        return next_obs, reward, terminal, valid
+
     def render(self, mode="human", arena=0):
         """The pygame window (RR_EnvBase.py:218-258) is UI and out of scope: 'human' is a no-op so callers' render()
         stays harmless; 'rgb_array' returns a CPU debug picture of ONE arena (arena width + 300-px dashboard strip like

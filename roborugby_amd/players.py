@@ -151,3 +151,35 @@ class Hive:
             for r in self.robots:
                 out3[:, r].copy_(thr[:, r])
         return out
+
+    # ---- training the hive in the full game (dqn.train_hive): act() -> env.step_thrust -> store()
+    @torch.no_grad()
+    def transition(self, done, status):
+        """The transition of every hive robot over the step taken since the last act(): ONE rr_hive_transition launch on the current
+        stream with the assignment act() made, into persistent buffers, no host synchronisation.  done, status: the step's.
+        -> (next_obs float32 [N,NR,11], reward float32 [N,NR], terminal bool [N,NR], valid bool [N,NR]); a row is valid when its robot
+        had a ball, the arena really stepped and the ball is still in play -- next_obs is the robot's view of THAT ball after the step.
+        The env must track the prior step (env.track_prior_step() before the step)."""
+        env = self.env
+        N, nr = env.num_envs, env.preset.nr
+        if getattr(self, "_next_obs", None) is None:
+            dev = env.device
+            self._next_obs = torch.zeros(N * nr, 11, dtype=torch.float32, device=dev)
+            self._reward = torch.zeros(N * nr, dtype=torch.float32, device=dev)
+            self._terminal = torch.zeros(N * nr, dtype=torch.bool, device=dev)
+            self._valid = torch.zeros(N * nr, dtype=torch.bool, device=dev)
+        env.hive_transition(self._assign, status, done, robot_mask=self.mask, observer=_OBSERVER_OF_KIND[self.kind],
+                            out=(self._next_obs, self._reward, self._terminal, self._valid))
+        return self._next_obs.view(N, nr, 11), self._reward.view(N, nr), self._terminal.view(N, nr), self._valid.view(N, nr)
+
+    @torch.no_grad()
+    def store(self, agent, done, status):
+        """transition() + ONE agent.store_transition over the N * NR rows: what the agent was asked on (obs), what it answered
+        (actions), reward, next_obs, terminal, valid= -- the store compacts the valid rows in (arena, robot) order.  Call it after
+        env.step_thrust and before the next act()."""
+        n = self.env.num_envs * self.env.preset.nr
+        self.transition(done, status)
+        agent.store_transition(self._obs[:n], self._actions[:n], self._reward, self._next_obs, self._terminal, valid=self._valid)
+
+
+_OBSERVER_OF_KIND = {0: "SingleBall_6wayLidar_v2", 1: "SingleBall_6wayLidar"}

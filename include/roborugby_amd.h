@@ -251,12 +251,42 @@ int rr_track_prior_step(rr_env *env, int32_t on, void *stream);
  * Invalid rows: next_obs 0, reward 0, terminal 0, valid [N,NR] u8 0.  Every output element is written on every call.
  * Returns -1 (message in rr_last_error, nothing launched): null handle / pointer; empty mask or a mask bit >= NR; kind not 0 or 1;
  * prior-step tracking off; a handle that has (had) a step budget -- a parked arena's pre-step assignment is overwritten by the next
- * rr_hive_observe before its step completes.  Read-only on the records and the snapshot.  rr_hive_transition_f64 refuses RR_DTYPE_F32
+ * rr_hive_observe before its step completes (rr_hive_transition_held below is the entry for such a handle).  Read-only on the records and the snapshot.  rr_hive_transition_f64 refuses RR_DTYPE_F32
  * like rr_hive_observe_f64. */
 int rr_hive_transition(rr_env *env, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
                        float *next_obs, float *reward, uint8_t *terminal, uint8_t *valid, void *stream);
 int rr_hive_transition_f64(rr_env *env, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
                            double *next_obs, double *reward, uint8_t *terminal, uint8_t *valid, void *stream);
+
+/* The hive under the budgeted step: HELD ROWS.  On a handle with a step budget an arena's step may span several calls; the transition it
+ * completes belongs to the assignment it was given, the observation the agent was asked on and the action it answered before the step
+ * began.  These entries keep those three rows while the arena is parked.  Call order per step, all with the SAME assign, obs and
+ * accepted buffers:
+ *   rr_hive_observe_held -> rr_dqn_act (into a scratch `fresh`) -> rr_hive_commit -> rr_step_thrust -> rr_hive_transition_held
+ * Then (obs, accepted, reward, next_obs, terminal) of a valid row is the transition of the step the arena accepted, however many calls
+ * that step took, and each arena's stream of such transitions is the synchronous mode's bit for bit.
+ *
+ * rr_hive_observe_held: rr_hive_observe, except that an arena parked mid-step gets held[a] = 1 and its assign / obs rows are NOT
+ *   written; every other arena gets held[a] = 0 and the rows rr_hive_observe writes.  held [N] u8, required.  The parked mark is read
+ *   from the arena's record, not from a status: a reset / rr_set_state / rr_set_poses of a parked arena clears it and the arena is
+ *   observed afresh.  On a handle that never had a budget: rr_hive_observe with held all 0.
+ * rr_hive_commit: the tail of the hive's turn.  fresh [N,NR] i32: the agent's answers to obs (rr_dqn_act); assign, held: as written
+ *   above.  For an arena that is not held and every robot r in robot_mask: accepted[a,r] = fresh[a,r], and thrust[a, 2r .. 2r+1] =
+ *   _dct_thrust_from_direction[fresh[a,r]] (RR_EnvBase.py:593-602) when assign[a,r] >= 0 and 0 <= fresh[a,r] < 8, else (0, 0) -- an
+ *   out-of-range value is never an index.  Nothing of a held arena is written (the step ignores its thrust), nor the columns of robots
+ *   outside the mask (another player drives them).  accepted [N,NR] i32, thrust [N,2*NR] f32.
+ * rr_hive_transition_held: rr_hive_transition -- same rows, bit for bit -- that is accepted on a handle with a step budget; an arena
+ *   that did not step (RR_STATUS_NOT_READY among them) is an invalid row and is written without reading its record.
+ * Guards as on rr_hive_observe / rr_hive_transition (-1, message in rr_last_error, nothing launched); launch-only: no allocation, no
+ * synchronisation.  The _f64 entries refuse RR_DTYPE_F32. */
+int rr_hive_observe_held(rr_env *env, uint32_t robot_mask, int32_t kind, int32_t *assign, float *obs, uint8_t *held, void *stream);
+int rr_hive_observe_held_f64(rr_env *env, uint32_t robot_mask, int32_t kind, int32_t *assign, double *obs, uint8_t *held, void *stream);
+int rr_hive_commit(rr_env *env, uint32_t robot_mask, const int32_t *fresh, const int32_t *assign, const uint8_t *held, int32_t *accepted,
+                   float *thrust, void *stream);
+int rr_hive_transition_held(rr_env *env, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status,
+                            const uint8_t *done, float *next_obs, float *reward, uint8_t *terminal, uint8_t *valid, void *stream);
+int rr_hive_transition_held_f64(rr_env *env, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status,
+                                const uint8_t *done, double *next_obs, double *reward, uint8_t *terminal, uint8_t *valid, void *stream);
 
 /* Opt-in goal scoring -- an EXTENSION: on the reference's live path the goals never score (Goal.track_balls / update_score are
  * only reached from the never-called GameEnv.__old_step, RR_EnvBase.py:458-520; RR_Goal.py:80 calls a property as a function),

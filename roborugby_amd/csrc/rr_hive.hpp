@@ -222,4 +222,55 @@ RR_HD void hive_transition(Arena<C> &A, const Rec<C> &q, const SimParams<typenam
     }
 }
 
+// ---- the hive under the budgeted step: held rows.
+//
+// Under a step budget an arena's step may span several calls (rr_sim.hpp: park_save).  While it is parked its record holds the middle
+// of that step, and the step ignores whatever thrust it is given.  The transition the arena completes later belongs to the assignment
+// it was given, the observation the agent was asked on and the action it answered BEFORE the step began -- so those three rows are held
+// while the arena is parked: hive_hold() keeps the observer off them, hive_commit() keeps the agent's fresh (wasted) answer out of them,
+// and hive_idle() writes the "no transition yet" row without touching the record.  The parked mark is read from the record
+// (record_parked), not from a caller's status: whatever rewrites an arena from outside clears it, and the arena is observed afresh.
+
+// held[0] = the arena is parked mid-step (irec: the int part of its record); true: the caller leaves the arena's assign / obs rows alone
+template <class C> RR_HD bool hive_hold(const int32_t *irec, uint8_t *held) {
+    const bool parked = record_parked<C>(irec); // (uniform over the arena's lanes: one word of its record)
+    RR_FOR_LANES(l) { if (l == 0) held[0] = parked ? 1 : 0; }
+    return parked;
+}
+
+// GameEnv_Simple._dct_thrust_from_direction (RR_EnvBase.py:593-602): Direction 0..7 -> (L, R); anything else is no direction: (0, 0)
+RR_HD void thrust_from_direction(int32_t dir, float &tl, float &tr) {
+    const float t[8][2] = { { 1.f, 1.f }, { -1.f, -1.f }, { -1.f, 1.f }, { 1.f, -1.f }, { 0.f, 1.f }, { 1.f, 0.f }, { -1.f, 0.f }, { 0.f, -1.f } };
+    const bool ok = dir >= 0 && dir < 8;
+    const int k = ok ? dir : 0; // (an out-of-range value is never an index)
+    tl = ok ? t[k][0] : 0.f;
+    tr = ok ? t[k][1] : 0.f;
+}
+
+// The tail of the hive's turn for ONE (arena, robot) cell -- no record needed: the agent's fresh answer is accepted unless the arena is
+// held.  fresh / assign / accepted [NR] and thrust [2 NR] of the arena, held its byte.  A held arena and a robot outside the mask keep
+// their accepted action and their thrust pair (another player drives the latter); a robot without a ball stands still.
+RR_HD void hive_commit(uint32_t robot_mask, int r, const int32_t *fresh, const int32_t *assign, uint8_t held, int32_t *accepted,
+                       float *thrust) {
+    if (held || !((robot_mask >> r) & 1u)) return;
+    const int32_t f = fresh[r];
+    accepted[r] = f;
+    float tl, tr;
+    thrust_from_direction(assign[r] >= 0 ? f : -1, tl, tr);
+    thrust[2 * r] = tl;
+    thrust[2 * r + 1] = tr;
+}
+
+// An arena whose status says it did not step (re-placed, parked, stepped after done) has no transition: the rows hive_transition
+// writes for it -- all 0 -- without its record.  false: the arena stepped, nothing was written.
+template <class C, typename O>
+RR_HD bool hive_idle(int32_t status, O *next_obs, O *reward, uint8_t *terminal, uint8_t *valid) {
+    if (!(status & (ST_WAS_RESET | ST_NOT_READY | ST_STEP_AFTER_DONE))) return false;
+    for (int base = 0; base < 11 * C::NR; base += C::VW) { RR_FOR_LANES(l) { if (base + l < 11 * C::NR) next_obs[base + l] = (O)0; } }
+    RR_FOR_LANES(l) {
+        if (l < C::NR) { reward[l] = (O)0; terminal[l] = 0; valid[l] = 0; }
+    }
+    return true;
+}
+
 } // namespace rr

@@ -334,10 +334,42 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
     Rec<C> q = { rec };
     hive_observe<C, O, KIND>(A, q, sp, robot_mask, assign + (size_t)arena * C::NR, obs + (size_t)arena * C::NR * 11);
 }
+// The same under the budgeted step (rr_hive.hpp: "held rows"): an arena parked mid-step keeps its assign / obs rows -- they belong to the
+// step it is in the middle of -- and says so in held[arena]; every other arena is observed exactly as k_hive does it.  The return is per
+// virtual wave, where the `arena >= n` one sits: nothing below exchanges data with the lanes of another arena (vw_argmin's butterfly has
+// width VW, RR_VOTE takes the group's share of the ballot, the LDS slice is the arena's own).
+template <class C, typename O, int KIND>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void k_hive_held(SimParams<typename C::Real> sp, const typename C::Store *recs,
+                                                                   const int32_t *irecs, int n, uint32_t robot_mask, int32_t *assign,
+                                                                   O *obs, uint8_t *held) {
+    __shared__ Arena<C> lds[arenas_per_block<C>()];
+    const int wave = threadIdx.x / C::VW; // virtual wave = arena slot in this workgroup
+    const int arena = blockIdx.x * arenas_per_block<C>() + wave;
+    if (arena >= n || wave >= arenas_per_block<C>()) return;
+    const int32_t *irec = irecs + (size_t)arena * Arena<C>::I_STRIDE;
+    if (hive_hold<C>(irec, held + arena)) return;
+    Arena<C> &A = lds[wave];
+    const typename C::Store *rec = recs + (size_t)arena * Arena<C>::P_STRIDE;
+    load_record(A, rec, irec);
+    if (KIND == OBS_V2) derive(A, sp);
+    Rec<C> q = { rec };
+    hive_observe<C, O, KIND>(A, q, sp, robot_mask, assign + (size_t)arena * C::NR, obs + (size_t)arena * C::NR * 11);
+}
+// The accepted action and the thrust pair of every (arena, robot) cell (rr_hive.hpp: hive_commit); one thread per cell, no record.
+__global__ __launch_bounds__(256) void k_hive_commit(int n, int nr, uint32_t robot_mask, const int32_t *fresh, const int32_t *assign,
+                                                     const uint8_t *held, int32_t *accepted, float *thrust) {
+    const int cell = blockIdx.x * 256 + threadIdx.x; // (n * nr <= 2^31 - 1: rr_hive_commit checks)
+    if (cell >= n * nr) return;
+    const int a = cell / nr, r = cell - a * nr;
+    const size_t row = (size_t)a * nr;
+    hive_commit(robot_mask, r, fresh + row, assign + row, held[a], accepted + row, thrust + 2 * row);
+}
 // Training the hive (rr_hive.hpp: hive_transition): after a step, every hive robot's next observation of the ball it was going for, its
 // reward, terminal and valid flag, in one launch next to k_hive -- same geometry, same launch bounds, same loads.  Read-only on the
 // records and on the on_step_begin snapshot `xs` (rr_track_prior_step keeps it); no atomics, every output element is written.
-template <class C, typename O, int KIND>
+// HELD (rr_hive_transition_held, "k_hive_transition_held"): an arena whose status says it did not step writes its zero rows and returns
+// before its record is loaded -- under a step budget those arenas are the many, not the few.  Same outputs either way.
+template <class C, typename O, int KIND, bool HELD = false>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void k_hive_transition(
     SimParams<typename C::Real> sp, const typename C::Store *recs, const int32_t *irecs, int n, const typename C::Real *xs, uint32_t robot_mask,
     const int32_t *assign, const int32_t *status, const uint8_t *done, O *next_obs, O *reward, uint8_t *terminal, uint8_t *valid) {
@@ -345,12 +377,15 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
     const int wave = threadIdx.x / C::VW; // virtual wave = arena slot in this workgroup
     const int arena = blockIdx.x * arenas_per_block<C>() + wave;
     if (arena >= n || wave >= arenas_per_block<C>()) return;
+    const size_t row = (size_t)arena * C::NR;
+    if constexpr (HELD) { // (per virtual wave, like the return above)
+        if (hive_idle<C, O>(status[arena], next_obs + row * 11, reward + row, terminal + row, valid + row)) return;
+    }
     Arena<C> &A = lds[wave];
     const typename C::Store *rec = recs + (size_t)arena * Arena<C>::P_STRIDE;
     load_record(A, rec, irecs + (size_t)arena * Arena<C>::I_STRIDE);
     if (KIND == OBS_V2) derive(A, sp);
     Rec<C> q = { rec };
-    const size_t row = (size_t)arena * C::NR;
     hive_transition<C, O, KIND>(A, q, sp, xs + (size_t)arena * xs_stride<C>(), robot_mask, assign + row, status[arena], done[arena],
                                 next_obs + row * 11, reward + row, terminal + row, valid + row);
 }
@@ -855,38 +890,49 @@ static int observe_impl(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, O *
         return 0;
     }, "rr_observe_f64: handle was created with RR_DTYPE_F32");
 }
-template <typename O>
-static int hive_observe_impl(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, O *obs, void *stream) {
-    if (!e || !assign || !obs) return fail(-1, "rr_hive_observe: null argument");
-    if (kind != OBS_V2 && kind != OBS_V1) return fail(-1, "rr_hive_observe: observer kind must be 0 (SingleBall_6wayLidar_v2) or 1 (SingleBall_6wayLidar)");
+// the argument checks the hive entries share; `who`: the entry's name in the message
+static int check_hive_args(rr_env *e, bool pointers, uint32_t robot_mask, int32_t kind, const std::string &who) {
+    if (!e || !pointers) return fail(-1, who + ": null argument");
+    if (kind != OBS_V2 && kind != OBS_V1) return fail(-1, who + ": observer kind must be 0 (SingleBall_6wayLidar_v2) or 1 (SingleBall_6wayLidar)");
     const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy;
-    if (!robot_mask) return fail(-1, "rr_hive_observe: empty robot mask");
-    if (nr < 32 && (robot_mask >> nr)) return fail(-1, "rr_hive_observe: robot mask has a bit at or above the number of robots");
-    return on_handle<O>(e, "rr_hive_observe", stream, [&](auto v) {
-        using C = typename decltype(v)::Cfg;
-        v.per_wave(kind == OBS_V2 ? k_hive<C, O, OBS_V2> : k_hive<C, O, OBS_V1>, v.sp(), v.recs(), v.irecs(), v.n(), robot_mask, assign, obs);
-        return 0;
-    }, "rr_hive_observe_f64: handle was created with RR_DTYPE_F32");
+    if (!robot_mask) return fail(-1, who + ": empty robot mask");
+    if (nr < 32 && (robot_mask >> nr)) return fail(-1, who + ": robot mask has a bit at or above the number of robots");
+    return 0;
 }
+// held != null: rr_hive_observe_held (k_hive_held)
+template <typename O>
+static int hive_observe_impl(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, O *obs, uint8_t *held, bool want_held, void *stream) {
+    const char *who = want_held ? "rr_hive_observe_held" : "rr_hive_observe";
+    if (int rc = check_hive_args(e, assign && obs && (held || !want_held), robot_mask, kind, who)) return rc;
+    return on_handle<O>(e, who, stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        if (want_held)
+            v.per_wave(kind == OBS_V2 ? k_hive_held<C, O, OBS_V2> : k_hive_held<C, O, OBS_V1>, v.sp(), v.recs(), v.irecs(), v.n(), robot_mask,
+                       assign, obs, held);
+        else
+            v.per_wave(kind == OBS_V2 ? k_hive<C, O, OBS_V2> : k_hive<C, O, OBS_V1>, v.sp(), v.recs(), v.irecs(), v.n(), robot_mask, assign, obs);
+        return 0;
+    }, want_held ? "rr_hive_observe_held_f64: handle was created with RR_DTYPE_F32" : "rr_hive_observe_f64: handle was created with RR_DTYPE_F32");
+}
+// held: rr_hive_transition_held -- accepted on a handle with a step budget (the caller holds the rows: see the header)
 template <typename O>
 static int hive_transition_impl(rr_env *e, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
-                                O *next_obs, O *reward, uint8_t *terminal, uint8_t *valid, void *stream) {
-    if (!e || !assign || !status || !done || !next_obs || !reward || !terminal || !valid) return fail(-1, "rr_hive_transition: null argument");
-    if (kind != OBS_V2 && kind != OBS_V1)
-        return fail(-1, "rr_hive_transition: observer kind must be 0 (SingleBall_6wayLidar_v2) or 1 (SingleBall_6wayLidar)");
-    const int nr = e->cfg.nr_happy + e->cfg.nr_grumpy;
-    if (!robot_mask) return fail(-1, "rr_hive_transition: empty robot mask");
-    if (nr < 32 && (robot_mask >> nr)) return fail(-1, "rr_hive_transition: robot mask has a bit at or above the number of robots");
+                                O *next_obs, O *reward, uint8_t *terminal, uint8_t *valid, bool held, void *stream) {
+    const std::string who = held ? "rr_hive_transition_held" : "rr_hive_transition";
+    if (int rc = check_hive_args(e, assign && status && done && next_obs && reward && terminal && valid, robot_mask, kind, who)) return rc;
     if (!(e->track_prior && e->xs))
-        return fail(-1, "rr_hive_transition: needs rr_track_prior_step(env, 1) before the step it looks back on (the rewards read the on_step_begin copies)");
-    if (e->park) // (a parked arena's pre-step assignment is overwritten by the next rr_hive_observe before its step completes)
+        return fail(-1, who + ": needs rr_track_prior_step(env, 1) before the step it looks back on (the rewards read the on_step_begin copies)");
+    if (e->park && !held) // (a parked arena's pre-step assignment is overwritten by the next rr_hive_observe before its step completes)
         return fail(-1, "rr_hive_transition: not on a handle with a step budget (arenas may be parked mid-step)");
-    return on_handle<O>(e, "rr_hive_transition", stream, [&](auto v) {
+    return on_handle<O>(e, who.c_str(), stream, [&](auto v) {
         using C = typename decltype(v)::Cfg;
-        v.per_wave(kind == OBS_V2 ? k_hive_transition<C, O, OBS_V2> : k_hive_transition<C, O, OBS_V1>, v.sp(), v.recs(), v.irecs(), v.n(), v.xs(),
-                   robot_mask, assign, status, done, next_obs, reward, terminal, valid);
+        auto launch = [&](auto kernel) {
+            v.per_wave(kernel, v.sp(), v.recs(), v.irecs(), v.n(), v.xs(), robot_mask, assign, status, done, next_obs, reward, terminal, valid);
+        };
+        if (held) launch(kind == OBS_V2 ? k_hive_transition<C, O, OBS_V2, true> : k_hive_transition<C, O, OBS_V1, true>);
+        else launch(kind == OBS_V2 ? k_hive_transition<C, O, OBS_V2> : k_hive_transition<C, O, OBS_V1>);
         return 0;
-    }, "rr_hive_transition_f64: handle was created with RR_DTYPE_F32");
+    }, held ? "rr_hive_transition_held_f64: handle was created with RR_DTYPE_F32" : "rr_hive_transition_f64: handle was created with RR_DTYPE_F32");
 }
 } // extern "C++"
 int rr_observe_kind(rr_env *e, int32_t kind, int32_t team, int32_t ridx, int32_t bidx, float *obs, int32_t out_dim, void *stream) {
@@ -898,18 +944,43 @@ int rr_observe_kind_f64(rr_env *e, int32_t kind, int32_t team, int32_t ridx, int
 int rr_observe(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, float *obs, void *stream) { return observe_impl<float>(e, team, ridx, bidx, obs, stream); }
 int rr_observe_f64(rr_env *e, int32_t team, int32_t ridx, int32_t bidx, double *obs, void *stream) { return observe_impl<double>(e, team, ridx, bidx, obs, stream); }
 int rr_hive_observe(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, float *obs, void *stream) {
-    return hive_observe_impl<float>(e, robot_mask, kind, assign, obs, stream);
+    return hive_observe_impl<float>(e, robot_mask, kind, assign, obs, nullptr, false, stream);
 }
 int rr_hive_observe_f64(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, double *obs, void *stream) {
-    return hive_observe_impl<double>(e, robot_mask, kind, assign, obs, stream);
+    return hive_observe_impl<double>(e, robot_mask, kind, assign, obs, nullptr, false, stream);
+}
+int rr_hive_observe_held(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, float *obs, uint8_t *held, void *stream) {
+    return hive_observe_impl<float>(e, robot_mask, kind, assign, obs, held, true, stream);
+}
+int rr_hive_observe_held_f64(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, double *obs, uint8_t *held, void *stream) {
+    return hive_observe_impl<double>(e, robot_mask, kind, assign, obs, held, true, stream);
+}
+int rr_hive_commit(rr_env *e, uint32_t robot_mask, const int32_t *fresh, const int32_t *assign, const uint8_t *held, int32_t *accepted,
+                   float *thrust, void *stream) {
+    if (int rc = check_hive_args(e, fresh && assign && held && accepted && thrust, robot_mask, OBS_V2, "rr_hive_commit")) return rc;
+    const int n = e->cfg.num_envs, nr = e->cfg.nr_happy + e->cfg.nr_grumpy;
+    if ((int64_t)n * nr > 0x7FFFFFFFll - 256) return fail(-1, "rr_hive_commit: too many (arena, robot) cells for one launch");
+    DeviceGuard guard(e->cfg.device);
+    hipLaunchKernelGGL(k_hive_commit, dim3((unsigned)((n * nr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, nr, robot_mask, fresh, assign,
+                       held, accepted, thrust);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 int rr_hive_transition(rr_env *e, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
                        float *next_obs, float *reward, uint8_t *terminal, uint8_t *valid, void *stream) {
-    return hive_transition_impl<float>(e, robot_mask, kind, assign, status, done, next_obs, reward, terminal, valid, stream);
+    return hive_transition_impl<float>(e, robot_mask, kind, assign, status, done, next_obs, reward, terminal, valid, false, stream);
 }
 int rr_hive_transition_f64(rr_env *e, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
                            double *next_obs, double *reward, uint8_t *terminal, uint8_t *valid, void *stream) {
-    return hive_transition_impl<double>(e, robot_mask, kind, assign, status, done, next_obs, reward, terminal, valid, stream);
+    return hive_transition_impl<double>(e, robot_mask, kind, assign, status, done, next_obs, reward, terminal, valid, false, stream);
+}
+int rr_hive_transition_held(rr_env *e, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
+                            float *next_obs, float *reward, uint8_t *terminal, uint8_t *valid, void *stream) {
+    return hive_transition_impl<float>(e, robot_mask, kind, assign, status, done, next_obs, reward, terminal, valid, true, stream);
+}
+int rr_hive_transition_held_f64(rr_env *e, uint32_t robot_mask, int32_t kind, const int32_t *assign, const int32_t *status, const uint8_t *done,
+                                double *next_obs, double *reward, uint8_t *terminal, uint8_t *valid, void *stream) {
+    return hive_transition_impl<double>(e, robot_mask, kind, assign, status, done, next_obs, reward, terminal, valid, true, stream);
 }
 
 int rr_set_state(rr_env *e, const double *robots, const int32_t *ri, const double *balls, const int32_t *step, void *stream) {

@@ -602,14 +602,18 @@ def train(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkp
 
 
 @torch.no_grad()
-def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, epsilon=0.2, preset="G"):
+def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, epsilon=0.2, preset="G", step_budget_clocks=0):
     """A checkpoint written by train() plays the full game: the happy team is the hive (players.Hive: the reference's
     DQN_pytorch_player.Stephen -- one policy, one ball per robot), the grumpy team is OG_Twitchy, the line-up of the reference's
     main.py without its human.  Returns mean return per team over the steps played (per finished episode when any finished) and
-    env-steps/s (HIP events around the loop: policy + step)."""
+    env-steps/s (HIP events around the loop: policy + step).  step_budget_clocks > 0: the budgeted step -- the hive holds the rows of
+    arenas parked mid-step (players.Hive), a call's rewards count for the arenas whose step completed in it, and env-steps are the rows
+    that stepped an arena (neither re-placed nor NOT_READY), as in train()."""
     import roborugby_amd as rr
+    from .env import STATUS_NOT_READY, STATUS_WAS_RESET
     from .players import Hive, og_twitchy
-    env = rr.BatchedRoboRugbyEnv(num_envs, preset=preset, device=device, seed=seed, action_mode="thrust")
+    env = rr.BatchedRoboRugbyEnv(num_envs, preset=preset, device=device, seed=seed, action_mode="thrust",
+                                 step_budget_clocks=step_budget_clocks)
     p = env.preset
     agent = BatchedDQNAgent(batch_size=64, max_mem_size=64, device=device, seed=seed)
     agent.load_state_dict(torch.load(checkpoint, map_location=device)["agent"])
@@ -620,6 +624,8 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
     thrust = torch.zeros(num_envs, 2 * p.nr, dtype=torch.float32, device=env.device)
     total_h = torch.zeros(num_envs, dtype=torch.float64, device=env.device)
     total_g = torch.zeros(num_envs, dtype=torch.float64, device=env.device)
+    real_rows = torch.zeros((), dtype=torch.int64, device=env.device)
+    parked_rows = torch.zeros((), dtype=torch.int64, device=env.device)
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     for _ in range(steps):
@@ -627,8 +633,15 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
             thrust[:, 2 * p.nr_happy:] = og_twitchy(num_envs, p.nr_grumpy, generator=gen, device=env.device)
         hive.act(out=thrust)
         _, reward, _, info = env.step_thrust(thrust)
-        total_h += reward
-        total_g += info.dblGrumpyScore
+        if step_budget_clocks:  # (a NOT_READY row's reward is not written by the step)
+            ready = (info.status & STATUS_NOT_READY) == 0
+            total_h += torch.where(ready, reward, 0.0)
+            total_g += torch.where(ready, info.dblGrumpyScore, 0.0)
+            parked_rows += (~ready).sum()
+            real_rows += ((info.status & (STATUS_WAS_RESET | STATUS_NOT_READY)) == 0).sum()
+        else:
+            total_h += reward
+            total_g += info.dblGrumpyScore
     t1.record()
     torch.cuda.synchronize(env.device)
     secs = t0.elapsed_time(t1) / 1e3
@@ -638,7 +651,9 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
                return_happy=float(total_h.mean()), return_grumpy=float(total_g.mean()), episodes_finished=int(cnt.sum()),
                episode_return_happy=float(lr[done].mean()) if bool(done.any()) else None,
                episode_return_grumpy=float(lrg[done].mean()) if bool(done.any()) else None,
-               env_steps_per_s=num_envs * steps / secs)
+               env_steps_per_s=(int(real_rows) if step_budget_clocks else num_envs * steps) / secs,
+               step_budget_clocks=step_budget_clocks, stepped_rows=int(real_rows) if step_budget_clocks else num_envs * steps,
+               not_ready_share=int(parked_rows) / max(num_envs * steps, 1))
     hive.close()
     env.close()
     return res
@@ -647,7 +662,7 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
 def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og_twitchy", resume=None, checkpoint=None,
                updates_per_step=4, device="cuda:0", seed=0, dtype="f64", batch_size=None, mem_size=None, replay_vector_steps=32,
                target_sync_vector_steps=64, eps_dec=.999997, eps_end=0.2, epsilon=None, learn=True, log_every=50, out=None,
-               observer=None):
+               observer=None, step_budget_clocks=0):
     """Training the hive mind IN the full game: one agent, one transition per hive robot and step.  Per vector step, serial on one
     stream: hive.epsilon = agent.epsilon -> `opponents` ('og_twitchy' or None = stand still) fill the other robots' thrust columns ->
     hive.act -> env.step_thrust -> hive.store (rr_hive_transition + one rr_dqn_store over the N * NR rows) -> updates_per_step x
@@ -655,12 +670,17 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
     robot's view of the ball it was going for; rows without a ball / of re-placed arenas are no transitions.
     robots: the hive (None: the happy team).  resume: a checkpoint of train() or of this function -- the AGENT is taken from it (a policy
     trained in preset T is fine-tuned in G), the env starts fresh.  The checkpoint written is one play_hive reads.  Returns a dict like
-    train()'s: throughput (HIP events around the loop), transitions stored, valid share, epsilon, mean per-robot reward."""
+    train()'s: throughput (HIP events around the loop), transitions stored, valid share, epsilon, mean per-robot reward.
+    step_budget_clocks > 0: the budgeted step.  A call no longer waits for its slowest arena; an arena whose step is still in progress
+    reports NOT_READY, the hive holds its rows (players.Hive) and the transition is stored by the call that completes the step, with the
+    observation and the action the arena accepted.  env-steps are then the rows that stepped an arena, as in train()."""
     import roborugby_amd as rr
+    from .env import STATUS_NOT_READY, STATUS_WAS_RESET
     from .players import Hive, og_twitchy
     if opponents not in ("og_twitchy", None):
         raise ValueError("opponents: 'og_twitchy' or None")
-    env = rr.BatchedRoboRugbyEnv(num_envs, preset=preset, device=device, seed=seed, dtype=dtype, action_mode="thrust")
+    env = rr.BatchedRoboRugbyEnv(num_envs, preset=preset, device=device, seed=seed, dtype=dtype, action_mode="thrust",
+                                 step_budget_clocks=step_budget_clocks)  # (refuses dtype 'f32_state' with a budget)
     env.track_prior_step()  # the rewards look back on every robot's and ball's position at the step's begin
     p = env.preset
     members = tuple(range(p.nr_happy)) if robots is None else tuple(sorted({int(r) for r in robots}))
@@ -680,6 +700,8 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
     thrust = torch.zeros(num_envs, 2 * p.nr, dtype=torch.float32, device=env.device)
     valid_rows = torch.zeros((), dtype=torch.int64, device=env.device)
     reward_sum = torch.zeros((), dtype=torch.float64, device=env.device)
+    real_rows = torch.zeros((), dtype=torch.int64, device=env.device)  # rows that stepped an arena (not re-placed, not NOT_READY)
+    parked_rows = torch.zeros((), dtype=torch.int64, device=env.device)
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     for i in range(steps):
@@ -696,6 +718,9 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
             hive.transition(done, info.status)
         valid_rows += hive._valid.sum()
         reward_sum += hive._reward.sum(dtype=torch.float64)  # (invalid rows carry 0)
+        if step_budget_clocks:
+            real_rows += ((info.status & (STATUS_WAS_RESET | STATUS_NOT_READY)) == 0).sum()
+            parked_rows += ((info.status & STATUS_NOT_READY) != 0).sum()
         if log_every and (i + 1) % log_every == 0:
             torch.cuda.synchronize(env.device)
             print(f"step {i + 1} epsilon {agent.epsilon:.6f} stored {agent.mem_cntr} updates {agent.updates} mean-robot-reward "
@@ -709,7 +734,9 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
         torch.save(dict(agent=agent.state_dict(), mode="train_hive", preset=preset, hive_robots=list(members)), checkpoint)
     n_valid = int(valid_rows.item())
     res = dict(mode="train_hive", preset=preset, dtype=dtype, num_envs=num_envs, steps=steps, hive_robots=list(members), opponents=opponents,
-               env_steps_per_sec=num_envs * steps / secs, seconds=secs, ms_per_vector_step=1e3 * secs / max(steps, 1),
+               env_steps_per_sec=(int(real_rows) if step_budget_clocks else num_envs * steps) / secs, seconds=secs,
+               ms_per_vector_step=1e3 * secs / max(steps, 1), step_budget_clocks=step_budget_clocks, stepped_rows=int(real_rows) if step_budget_clocks else num_envs * steps,
+               not_ready_share=int(parked_rows) / max(num_envs * steps, 1),
                transitions=int(agent.mem_cntr) if learn else 0, valid_rows=n_valid, valid_share=n_valid / max(rows * steps, 1),
                epsilon=agent.epsilon, mean_robot_reward=float(reward_sum.item()) / max(n_valid, 1), learn_calls=agent.updates,
                updates_per_step=updates_per_step if learn else 0, batch_size=B, replay_transitions=agent.mem_size,
@@ -752,12 +779,12 @@ def main():
                          "any checkpoint, e.g. one trained in preset T (--num-envs, --steps, --checkpoint, --updates-per-step, --batch-size)")
     a = ap.parse_args()
     if a.play_hive:
-        print(json.dumps(play_hive(a.play_hive, a.num_envs, a.steps, a.device, a.seed, preset=a.preset or "G")))
+        print(json.dumps(play_hive(a.play_hive, a.num_envs, a.steps, a.device, a.seed, preset=a.preset or "G", step_budget_clocks=a.budget)))
         return
     if a.train_hive:
         print(json.dumps(train_hive(a.num_envs, a.steps, a.preset or "G", resume=a.resume, checkpoint=a.checkpoint,
                                     updates_per_step=a.updates_per_step, device=a.device, seed=a.seed, batch_size=a.batch_size,
-                                    eps_dec=a.eps_dec, learn=not a.no_learn, log_every=a.log_every, out=a.out)))
+                                    eps_dec=a.eps_dec, learn=not a.no_learn, log_every=a.log_every, out=a.out, step_budget_clocks=a.budget)))
         return
     res = train(a.num_envs, a.steps, a.preset or "T", a.device, a.seed, a.checkpoint, a.resume, learn=not a.no_learn,
                 updates_per_step=a.updates_per_step, batch_size=a.batch_size, eps_dec=a.eps_dec, eval_every=a.eval_every,

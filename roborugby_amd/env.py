@@ -411,26 +411,61 @@ class BatchedRoboRugbyEnv:
         _lib.check(fn(self._h, kind, team, int(robot_idx), int(ball_idx), _ptr(obs), dim, self._stream()), "rr_observe_kind", self._lib)
         return obs
 
-    def hive_observe(self, robot_mask=None, observer=None, f64=False, out=None):
+    @property
+    def has_had_budget(self):
+        """the handle has, or has had, a step budget: arenas may be parked mid-step (the hive then holds their rows)"""
+        return bool(self.step_budget_clocks) or self._bout is not None
+
+    def hive_observe(self, robot_mask=None, observer=None, f64=False, out=None, held=False):
         """The hive-mind player's view (DQN_pytorch_player.py: Stephen.__ponder + the observation __consult asks for) of every arena in
         one launch (rr_hive_observe): -> (assign int32 [N,NR], obs [N,NR,11]).  assign[a, r] is the ball robot r of arena a goes for --
         greedy, nearest (robot, ball) pair first, balls lying in a goal ignored -- or -1 (no ball left, or r is outside the hive);
         obs[a, r] = get_game_state(robot_idx=r, ball_idx=assign[a, r]) seen from r's own team, 0 where assign is -1.
         robot_mask: bit r = robot r belongs to the hive (None: every happy robot); observer: 'SingleBall_6wayLidar_v2' or
-        'SingleBall_6wayLidar' (None: the env's own when it is one of the two, else the former); out: (assign, obs) to reuse."""
+        'SingleBall_6wayLidar' (None: the env's own when it is one of the two, else the former); out: (assign, obs) to reuse.
+        held=True (rr_hive_observe_held, the budgeted step): -> (assign, obs, held uint8 [N]); the rows of an arena parked mid-step are
+        NOT written -- they stay what `out` holds, the rows of the step it is in the middle of -- and held is 1 there; out: (assign, obs,
+        held) to reuse (without `out` the rows of held arenas are 0 / -1)."""
         p, N = self.preset, self.num_envs
         mask = (1 << p.nr_happy) - 1 if robot_mask is None else int(robot_mask)
         kind = (self.obs_kind if self.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
-        if out is None:
-            out = (self._new((N, p.nr), torch.int32), self._new((N, p.nr, 11), torch.float64 if f64 else torch.float32))
-        assign, obs = out
+        od = torch.float64 if f64 else torch.float32
+        if out is None and held:
+            out = (torch.full((N, p.nr), -1, dtype=torch.int32, device=self.device), torch.zeros((N, p.nr, 11), dtype=od, device=self.device),
+                   self._new((N,), torch.uint8))
+        elif out is None:
+            out = (self._new((N, p.nr), torch.int32), self._new((N, p.nr, 11), od))
+        assign, obs = out[:2]
         assert assign.dtype == torch.int32 and assign.is_contiguous() and assign.numel() == N * p.nr
-        assert obs.dtype == (torch.float64 if f64 else torch.float32) and obs.is_contiguous() and obs.numel() >= N * p.nr * 11
+        assert obs.dtype == od and obs.is_contiguous() and obs.numel() >= N * p.nr * 11
         if mask < 0 or mask > 0xFFFFFFFF:
             raise ValueError("robot_mask: one bit per robot")
+        if held:
+            hl = out[2]
+            assert hl.dtype in (torch.uint8, torch.bool) and hl.is_contiguous() and hl.numel() == N and hl.device == self.device
+            fn = self._lib.rr_hive_observe_held_f64 if f64 else self._lib.rr_hive_observe_held
+            _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(obs), _ptr(hl), self._stream()), "rr_hive_observe_held", self._lib)
+            return assign, obs, hl
         fn = self._lib.rr_hive_observe_f64 if f64 else self._lib.rr_hive_observe
         _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(obs), self._stream()), "rr_hive_observe", self._lib)
         return assign, obs
+
+    def hive_commit(self, fresh, assign, held, accepted, thrust, robot_mask=None):
+        """The tail of the hive's turn under the budgeted step, in one launch (rr_hive_commit): for every arena that is not held and every
+        robot of the mask, accepted[a, r] = fresh[a, r] and thrust[a, 2r:2r+2] = the (L, R) pair of that direction -- (0, 0) without a ball
+        (assign < 0) or for a value outside 0..7.  Held arenas and robots outside the mask keep what `accepted` and `thrust` hold.
+        fresh, assign, accepted: int32 [N,NR]; held: uint8 [N] (hive_observe(held=True)); thrust: float32 [N,2*NR].  -> (accepted, thrust)"""
+        p, N = self.preset, self.num_envs
+        mask = (1 << p.nr_happy) - 1 if robot_mask is None else int(robot_mask)
+        for t in (fresh, assign, accepted):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= N * p.nr and t.device == self.device
+        assert held.dtype in (torch.uint8, torch.bool) and held.is_contiguous() and held.numel() == N and held.device == self.device
+        assert thrust.dtype == torch.float32 and thrust.is_contiguous() and thrust.numel() == N * 2 * p.nr and thrust.device == self.device
+        if mask < 0 or mask > 0xFFFFFFFF:
+            raise ValueError("robot_mask: one bit per robot")
+        _lib.check(self._lib.rr_hive_commit(self._h, mask, _ptr(fresh), _ptr(assign), _ptr(held), _ptr(accepted), _ptr(thrust), self._stream()),
+                   "rr_hive_commit", self._lib)
+        return accepted, thrust
 
     def track_prior_step(self, on=True):
         """rr_track_prior_step: every step from now on first snapshots what the sprites' on_step_begin copies (robot and ball centres at
@@ -445,7 +480,17 @@ class BatchedRoboRugbyEnv:
         is in the mask, was given a ball, the arena really stepped (not re-placed, not STEP_AFTER_DONE) and the ball is still in play;
         then next_obs is the robot's observation of THE SAME ball after the step, reward the per-robot reward defined in
         include/roborugby_amd.h and terminal = done.  Invalid rows are 0.  Needs track_prior_step() before the step; refuses a handle with
-        a step budget.  robot_mask / observer / f64 as in hive_observe; out: the four tensors to reuse."""
+        a step budget (hive_transition_held is the entry for one).  robot_mask / observer / f64 as in hive_observe; out: the four
+        tensors to reuse."""
+        return self._hive_transition("rr_hive_transition", assign, status, done, robot_mask, observer, f64, out)
+
+    def hive_transition_held(self, assign, status, done, robot_mask=None, observer=None, f64=False, out=None):
+        """hive_transition on a handle with a step budget (rr_hive_transition_held): the same rows, bit for bit -- for a caller that held
+        the rows of parked arenas (hive_observe(held=True) -> hive_commit, the same buffers every call): a valid row is then the
+        transition of the step the arena accepted, however many calls that step took.  Arguments as hive_transition's."""
+        return self._hive_transition("rr_hive_transition_held", assign, status, done, robot_mask, observer, f64, out)
+
+    def _hive_transition(self, name, assign, status, done, robot_mask, observer, f64, out):
         p, N = self.preset, self.num_envs
         mask = (1 << p.nr_happy) - 1 if robot_mask is None else int(robot_mask)
         kind = (self.obs_kind if self.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
@@ -462,9 +507,9 @@ class BatchedRoboRugbyEnv:
         assert all(t.dtype in (torch.uint8, torch.bool) and t.is_contiguous() and t.numel() >= N * p.nr for t in (terminal, valid))
         if mask < 0 or mask > 0xFFFFFFFF:
             raise ValueError("robot_mask: one bit per robot")
-        fn = self._lib.rr_hive_transition_f64 if f64 else self._lib.rr_hive_transition
+        fn = getattr(self._lib, name + ("_f64" if f64 else ""))
         _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(status), _ptr(done), _ptr(next_obs), _ptr(reward), _ptr(terminal), _ptr(valid),
-                      self._stream()), "rr_hive_transition", self._lib)
+                      self._stream()), name, self._lib)
         return next_obs, reward, terminal, valid
 
     def render(self, mode="human", arena=0):

@@ -47,7 +47,10 @@ class Hive:
     robot without a ball stands still (0, 0).
 
     act() is rr_hive_observe -> ONE rr_dqn_act over the N * NR rows (padded to a multiple of 64) -> table lookup, all on the current
-    stream: no host synchronisation, and with `out` given no allocation.  `agent`: a roborugby_amd.dqn.BatchedDQNAgent (its Q_eval
+    stream: no host synchronisation, and with `out` given no allocation.  On an env that has, or has had, a step budget
+    (env.has_had_budget) act() holds the rows of arenas parked mid-step instead: rr_hive_observe_held -> rr_dqn_act into a scratch
+    buffer -> rr_hive_commit, so `assign`, `obs` and `actions` of a parked arena stay those of the step it is in the middle of and
+    transition() / store() hand out the transition of the step the arena ACCEPTED; `held` says which arenas those were.  `agent`: a roborugby_amd.dqn.BatchedDQNAgent (its Q_eval
     acts) or the six parameter tensors (fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc3.weight, fc3.bias; float32, on the env's
     device).  `robots`: indices of the hive's robots, happy robots first (None: the happy team).  `observer`: what the agent was
     trained on -- None = the env's own when it is SingleBall_6wayLidar(_v2), else SingleBall_6wayLidar_v2 (what `dqn.train` uses;
@@ -82,12 +85,14 @@ class Hive:
         self._agent = agent  # (kept alive: a borrowed rr_dqn handle is the agent's)
         self.rows = (N * nr + 63) // 64 * 64
         dev = env.device
-        self._assign = torch.empty(N, nr, dtype=torch.int32, device=dev)
+        self._assign = torch.full((N, nr), -1, dtype=torch.int32, device=dev)  # (-1: an arena held from the very first act() has no row)
         self._obs = torch.zeros(self.rows, 11, dtype=torch.float32, device=dev)  # (the padding rows stay 0)
         self._actions = torch.zeros(self.rows, dtype=torch.int32, device=dev)
         self._thrust = torch.empty(N * nr, 2, dtype=torch.float32, device=dev)
         self._has = torch.empty(N, nr, dtype=torch.bool, device=dev)
         self._table = torch.tensor(_THRUST_FROM_DIRECTION, dtype=torch.float32, device=dev)
+        self._held = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._fresh = None  # the agent's answers before rr_hive_commit accepts them (budgeted step only)
         self.calls = 0
 
     def close(self):
@@ -116,11 +121,35 @@ class Hive:
         """int32 [N, NR]: the agent's answers of the last act() (meaningful where assign >= 0)"""
         return self._actions[:self.env.num_envs * self.env.preset.nr].view(self.env.num_envs, self.env.preset.nr)
 
+    @property
+    def held(self):
+        """bool [N]: arenas that were parked mid-step at the last act() on a budgeted env -- their assign / obs / actions rows were held"""
+        return self._held.view(torch.bool)
+
+    def _dqn_act(self, actions, stream):
+        from . import _lib
+        self.calls += 1
+        ptrs = (C.c_void_p * 6)(*[p.data_ptr() for p in self._params])
+        _lib.check_dqn(self._rrlib.rr_dqn_act(self._dqn_h, C.byref(ptrs), C.c_void_p(self._obs.data_ptr()), self.rows,
+                                              min(max(self.epsilon, 0.0), 1.0), self.seed, self.calls & 0xFFFFFFFF,
+                                              C.c_void_p(actions.data_ptr()), None, stream), "rr_dqn_act", self._rrlib)
+
+    def _act_held(self, out, stream):
+        """act() under the budgeted step: observe (held rows kept) -> the agent's fresh answers -> commit, on the current stream"""
+        env = self.env
+        if self._fresh is None:
+            self._fresh = torch.zeros(self.rows, dtype=torch.int32, device=env.device)
+        env.hive_observe(self.mask, _OBSERVER_OF_KIND[self.kind], out=(self._assign, self._obs, self._held), held=True)
+        self._dqn_act(self._fresh, stream)  # (held arenas waste their draws)
+        env.hive_commit(self._fresh, self._assign, self._held, self._actions, out, self.mask)
+        return out
+
     @torch.no_grad()
     def act(self, out=None, status=None):
         """float32 [N, 2*NR] thrust pairs for env.step_thrust.  Columns of robots outside the hive are left as the caller filled them
         in `out` (0 in a fresh tensor), so another player -- `og_twitchy` -- can drive them.  status (optional, the last step's
-        info.status): rows of arenas that are NOT_READY (budgeted step, parked mid-step) are left alone; the step ignores them."""
+        info.status): rows of arenas that are NOT_READY (budgeted step, parked mid-step) are left alone; the step ignores them.
+        Without `status`, on an env that has (had) a step budget: the held pipeline (see the class)."""
         from . import _lib
         env = self.env
         N, nr = env.num_envs, env.preset.nr
@@ -128,13 +157,11 @@ class Hive:
             out = torch.zeros(N, 2 * nr, dtype=torch.float32, device=env.device)
         assert out.dtype == torch.float32 and out.shape == (N, 2 * nr) and out.is_contiguous()
         stream = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+        if status is None and env.has_had_budget:
+            return self._act_held(out, stream)
         _lib.check(env._lib.rr_hive_observe(env._h, self.mask, self.kind, C.c_void_p(self._assign.data_ptr()),
                                             C.c_void_p(self._obs.data_ptr()), stream), "rr_hive_observe", env._lib)
-        self.calls += 1
-        ptrs = (C.c_void_p * 6)(*[p.data_ptr() for p in self._params])
-        _lib.check_dqn(self._rrlib.rr_dqn_act(self._dqn_h, C.byref(ptrs), C.c_void_p(self._obs.data_ptr()), self.rows,
-                                              min(max(self.epsilon, 0.0), 1.0), self.seed, self.calls & 0xFFFFFFFF,
-                                              C.c_void_p(self._actions.data_ptr()), None, stream), "rr_dqn_act", self._rrlib)
+        self._dqn_act(self._actions, stream)
         torch.index_select(self._table, 0, self._actions[:N * nr], out=self._thrust)
         torch.ge(self._assign, 0, out=self._has)
         thr = self._thrust.view(N, nr, 2)
@@ -159,7 +186,9 @@ class Hive:
         stream with the assignment act() made, into persistent buffers, no host synchronisation.  done, status: the step's.
         -> (next_obs float32 [N,NR,11], reward float32 [N,NR], terminal bool [N,NR], valid bool [N,NR]); a row is valid when its robot
         had a ball, the arena really stepped and the ball is still in play -- next_obs is the robot's view of THAT ball after the step.
-        The env must track the prior step (env.track_prior_step() before the step)."""
+        The env must track the prior step (env.track_prior_step() before the step).  On an env that has (had) a step budget this is
+        rr_hive_transition_held: a row of an arena whose step is still in progress is invalid, and the row of the call that completes
+        it pairs with the obs / actions act() held for it."""
         env = self.env
         N, nr = env.num_envs, env.preset.nr
         if getattr(self, "_next_obs", None) is None:
@@ -168,8 +197,9 @@ class Hive:
             self._reward = torch.zeros(N * nr, dtype=torch.float32, device=dev)
             self._terminal = torch.zeros(N * nr, dtype=torch.bool, device=dev)
             self._valid = torch.zeros(N * nr, dtype=torch.bool, device=dev)
-        env.hive_transition(self._assign, status, done, robot_mask=self.mask, observer=_OBSERVER_OF_KIND[self.kind],
-                            out=(self._next_obs, self._reward, self._terminal, self._valid))
+        fn = env.hive_transition_held if env.has_had_budget else env.hive_transition
+        fn(self._assign, status, done, robot_mask=self.mask, observer=_OBSERVER_OF_KIND[self.kind],
+           out=(self._next_obs, self._reward, self._terminal, self._valid))
         return self._next_obs.view(N, nr, 11), self._reward.view(N, nr), self._terminal.view(N, nr), self._valid.view(N, nr)
 
     @torch.no_grad()

@@ -318,6 +318,38 @@ int rr_episode_stats(rr_env *env, float *last_return, float *last_return_g, int3
 int rr_policy_chase(rr_env *env, const float *obs, const int32_t *step_of, uint32_t step, float noise, uint64_t seed,
                     int32_t *actions, int32_t na, void *stream);
 
+/* Pictures: RGB frames of many arenas in one launch, straight from the records (csrc/rr_render.hpp).  What render() draws on the host
+ * for one arena -- goals, robots, balls, in the colours of roborugby_amd/render.py -- without the dashboard strip, at any size: small
+ * enough to tile a running batch into a contact sheet, or to serve as a pixel observation.  An extension (the reference draws with pygame).
+ *
+ * The picture.  Arena coordinates, y down.  A frame shows the field only (W x H), scaled independently in x and y to width x height
+ * pixels, with S = `samples` (1, 2 or 4) samples per axis and pixel.  Sample (a, b) of pixel (i, j) is the point
+ *     x = ((float)(i*S + a) + 0.5f) * fx,   y = ((float)(j*S + b) + 0.5f) * fy,
+ *     fx = (float)(W / (double)(width*S)),  fy = (float)(H / (double)(height*S))        (fx, fy computed once on the host)
+ * -- a frame with S samples at `width` decides the same sample points as a frame with 1 sample at width*S.  A sample takes the colour of
+ * the topmost layer that contains it; boundaries are closed; all arithmetic is fp32 (a record's fp64 values are rounded first):
+ *   1. background (255, 255, 255);
+ *   2. goals (RR_Goal.py:14-28, 240 = GOAL_WIDTH): grumpy (242, 53, 87) where x + y <= 240; happy (43, 146, 228) where
+ *      (W - x) + (H - y) <= 240;
+ *   3. robots 0 .. NR-1, a later one over an earlier one.  th = radians(360 - rot), c = cos th, s = sin th, (dx, dy) = sample - centre,
+ *      u = dx*c + dy*s, v = -dx*s + dy*c (the inverse of render.robot_corners).  Inside: |u| <= 10 && |v| <= 20 -- the rectangle the
+ *      collision geometry uses.  Black (0, 0, 0) where |u| > 9 || |v| > 19; else yellow (255, 255, 0) where u > 7 (the front is the
+ *      RIGHT side, RR_Observers.py:322-324); else the team colour, (40, 90, 200) for robots below nr_happy, (200, 60, 60) for the others;
+ *   4. balls 0 .. NB-1, later over earlier.  Inside: dx*dx + dy*dy <= 49; black where > 36, else (80, 220, 100) for positive balls and
+ *      (60, 16, 83) for negative ones.
+ * An entity with a non-finite pose draws nothing; a ball consumed by goal scoring is parked at x <= -1000 and falls outside the frame by
+ * itself.  With S > 1 each channel is (sum of the S*S sample values + S*S/2) / (S*S) in integer arithmetic.  A frame whose arena index
+ * is outside 0 .. N-1 is written all zero (black, which no in-range frame of a white field is); such an index is never used as an index.
+ *
+ * arenas [m] i32 DEVICE pointer, NULL = arenas 0 .. m-1; duplicates and any order are allowed.  rgb [m, height, width, 3] u8, 4-byte
+ * aligned: every byte of the m frames is written on every call, and nothing beyond them.  Read-only on the records; accepted on every
+ * handle -- all three dtypes, both libraries and the one-shape libraries, and handles with a step budget: an arena parked mid-step shows
+ * its mid-step record, as rr_hive_observe does.  Returns -1 (rr_last_error) and launches nothing for a null handle or rgb, m outside
+ * 1 .. 1 << 20, width outside 4 .. 4096 or not a multiple of 4, height outside 1 .. 4096, samples not 1, 2 or 4, or a misaligned rgb.
+ * Launch-only: no allocation, no synchronisation (more than 65,535 frames go out as several launches on the same stream). */
+int rr_render(rr_env *env, const int32_t *arenas, int32_t m, int32_t width, int32_t height, int32_t samples,
+              uint8_t *rgb, void *stream);
+
 /* ---- config 5 (BASELINE.json): the learn step of the reference's DQN agent (Training_DQN_pytorch.py:25-67 DeepQNetwork
  * Linear 11 -> 256 -> 256 -> 8 + ReLU, MSELoss, Adam; :151-191 DQNAgent.learn) fused into two launches for the wide batches of the
  * batched trainer: forward of Q_eval(s) and Q_target(s'), TD target, loss gradient, backward and the weight-gradient reduction in

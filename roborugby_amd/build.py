@@ -15,7 +15,7 @@ SRC_KSTEP = os.path.join(HERE, "csrc", "rr_kstep_inst.hip")  # explicit instanti
 SRC_DQN = os.path.join(HERE, "csrc", "rr_dqn.hip")            # fused DQN update (config 5): its own translation unit
 HDR_KSTEP = os.path.join(HERE, "csrc", "rr_kstep.hpp")         # ... and the table of built configurations
 DEPS = [SRC, SRC_KSTEP, SRC_DQN, HDR_KSTEP, os.path.join(HERE, "csrc", "rr_sim.hpp"),
-        os.path.join(HERE, "csrc", "rr_extras.hpp"), os.path.join(HERE, "csrc", "rr_hive.hpp"),
+        os.path.join(HERE, "csrc", "rr_extras.hpp"), os.path.join(HERE, "csrc", "rr_hive.hpp"), os.path.join(HERE, "csrc", "rr_render.hpp"),
         os.path.join(os.path.dirname(HERE), "include", "roborugby_amd.h")]
 LIB = os.path.join(HERE, "libroborugby_amd.so")
 # the exact-trig parity build: the same sources with -DRR_EXACT_TRIG=1 (sin / cos of the robot kinematics in double-double, ~correctly

@@ -23,6 +23,7 @@
 #include "rr_sim.hpp"
 #include "rr_extras.hpp"
 #include "rr_hive.hpp"
+#include "rr_render.hpp"
 #include "rr_kstep.hpp"
 
 using namespace rr;
@@ -1055,6 +1056,35 @@ int rr_policy_chase(rr_env *e, const float *obs, const int32_t *step_of, uint32_
                        e->cfg.arena_offset, step_of, step, actions);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// Pictures (rr_render.hpp): one kernel for every configuration -- the record's layout travels as a runtime struct, filled here where the
+// handle's configuration is known.  Frames in blockIdx.y, at most 65,535 per launch.
+int rr_render(rr_env *e, const int32_t *arenas, int32_t m, int32_t width, int32_t height, int32_t samples, uint8_t *rgb, void *stream) {
+    if (!e) return fail(-1, "rr_render: null handle");
+    if (!rgb) return fail(-1, "rr_render: null rgb");
+    if (m < 1 || m > (1 << 20)) return fail(-1, "rr_render: between 1 and 1 << 20 frames");
+    if (width < 4 || width > 4096 || (width & 3)) return fail(-1, "rr_render: width must be a multiple of 4 in 4 .. 4096 (four pixels per thread)");
+    if (height < 1 || height > 4096) return fail(-1, "rr_render: height must be in 1 .. 4096");
+    if (samples != 1 && samples != 2 && samples != 4) return fail(-1, "rr_render: samples must be 1, 2 or 4");
+    if ((uintptr_t)rgb & 3) return fail(-1, "rr_render: rgb must be 4-byte aligned (the frames are stored as dwords)");
+    return on_handle(e, "rr_render", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        using L = RecLayout<C>;
+        static_assert(C::NR <= RENDER_MAX && C::NB <= RENDER_MAX && C::NR + C::NB <= RENDER_THREADS, "the draw list holds every entity");
+        const RenderLayout rl = { L::RCX, L::RCY, L::RROT, L::BCX, L::BCY, Arena<C>::P_STRIDE, C::NR, C::NRH, C::NB, C::NBP,
+                                  sizeof(typename C::Store) == 8 ? 1 : 0 };
+        const double W = e->cfg.arena_w, H = e->cfg.arena_h;
+        const RenderView rv = { (float)W, (float)H, (float)(W / (double)(width * samples)), (float)(H / (double)(height * samples)),
+                                width, height, samples };
+        const size_t quads = (size_t)width * (size_t)height / RENDER_QUAD;
+        const unsigned bx = (unsigned)((quads + RENDER_THREADS - 1) / RENDER_THREADS);
+        for (size_t f0 = 0; f0 < (size_t)m; f0 += 65535) {
+            const size_t nf = (size_t)m - f0 < 65535 ? (size_t)m - f0 : 65535;
+            hipLaunchKernelGGL(k_render, dim3(bx, (unsigned)nf), dim3(RENDER_THREADS), 0, v.s, rl, rv, (const void *)v.recs(), v.n(), arenas, f0, rgb);
+        }
+        return 0;
+    });
 }
 
 int rr_probe_hbm_copy(void *dst, const void *src, size_t bytes, void *stream) {

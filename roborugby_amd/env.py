@@ -524,6 +524,38 @@ class BatchedRoboRugbyEnv:
         st = self.get_state()
         return draw_arena(self.preset, st["robots"][arena].cpu().numpy(), st["balls"][arena].cpu().numpy())
 
+    RENDER_BATCH_MAX_BYTES = 1 << 30
+
+    def render_batch(self, arenas=None, width=None, height=None, samples=1, out=None):
+        """RGB frames of many arenas in one launch, straight from the records on the device (rr_render; the picture is specified in
+        include/roborugby_amd.h): -> uint8 [M, height, width, 3] on the env's device, enqueued on the current stream.  The field only --
+        no dashboard strip --, scaled independently in x and y; `samples` (1, 2 or 4) per axis and pixel, box-filtered.
+        arenas: an int tensor or a sequence of arena indices (any order, duplicates allowed; an index outside 0 .. N-1 gives an
+        all-zero frame), None: every arena.  width / height: None = the native int(arena_w) x int(arena_h); width a multiple of 4.
+        out: a contiguous uint8 tensor of M * height * width * 3 elements on the device to write into.  Raises ValueError before any
+        launch when the result would exceed 1 GiB."""
+        p = self.preset
+        w = int(p.arena_w) if width is None else int(width)
+        h = int(p.arena_h) if height is None else int(height)
+        idx = None
+        if arenas is not None:
+            idx = torch.as_tensor(arenas)
+            if idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 1:
+                raise ValueError("render_batch(arenas=...): a 1-D sequence of integer arena indices")
+            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        m = self.num_envs if idx is None else int(idx.numel())
+        if m < 1 or w < 1 or h < 1:
+            raise ValueError("render_batch: at least one frame of at least one pixel")
+        if m * h * w * 3 > self.RENDER_BATCH_MAX_BYTES:
+            raise ValueError(f"render_batch: {m} frames of {w}x{h} are {m * h * w * 3 / 2 ** 30:.2f} GiB, above the 1 GiB a call may write; "
+                             "render fewer arenas per call or smaller frames")
+        if out is None:
+            out = self._new((m, h, w, 3), torch.uint8)
+        elif not (out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == m * h * w * 3 and out.device == self.device):
+            raise ValueError(f"render_batch(out=...): a contiguous uint8 tensor of {m}x{h}x{w}x3 elements on {self.device}")
+        _lib.check(self._lib.rr_render(self._h, _ptr(idx), m, w, h, int(samples), _ptr(out), self._stream()), "rr_render", self._lib)
+        return out.view(m, h, w, 3)
+
     def seed(self, seed=None):
         """Like the reference (RR_EnvBase.py:568-570) this does not re-seed placement; the reset RNG is keyed at
         construction (`seed=`)."""

@@ -1,5 +1,6 @@
 """CPU debug picture of one arena (PIL).  Not the reference's pygame renderer (UI is out of scope): just enough to look
-at a state -- goals, robots as rotated 20x40 rectangles with their front edge marked, balls."""
+at a state -- goals, robots as rotated 20x40 rectangles with their front edge marked, balls.  Next to it, what turns the device's frames
+(BatchedRoboRugbyEnv.render_batch) into something to look at: contact_sheet tiles many arenas into one image, save_gif writes a clip."""
 import math
 
 import numpy as np
@@ -42,3 +43,37 @@ def draw_arena(preset, robots, balls):
         col = COLOR_BALL_POS if i < preset.nb_pos else COLOR_BALL_NEG
         d.ellipse([b[0] - 7, b[1] - 7, b[0] + 7, b[1] + 7], fill=col, outline=(0, 0, 0))
     return np.asarray(img)
+
+
+def contact_sheet(frames, cols=None, pad=2):
+    """Tiles frames [M, h, w, 3] (uint8; a torch tensor on any device, or numpy) into ONE image of `cols` columns (None: the smallest
+    square that holds them), `pad` grey pixels (the dashboard's fill) between the tiles and around the sheet; a tile without a frame stays grey.
+    The result lives where the input does: a tensor for a tensor, an array for an array."""
+    m, h, w, ch = frames.shape
+    if ch != 3 or m < 1:
+        raise ValueError("contact_sheet: frames [M, h, w, 3] with M >= 1")
+    cols = int(cols) if cols else int(math.ceil(math.sqrt(m)))
+    if cols < 1 or pad < 0:
+        raise ValueError("contact_sheet: at least one column and no negative padding")
+    rows = (m + cols - 1) // cols
+    shape = (pad + rows * (h + pad), pad + cols * (w + pad), 3)
+    if isinstance(frames, np.ndarray):
+        sheet = np.full(shape, COLOR_DASHBOARD_FILL[0], frames.dtype)
+    else:
+        sheet = frames.new_full(shape, COLOR_DASHBOARD_FILL[0])
+    for k in range(m):
+        y, x = pad + (k // cols) * (h + pad), pad + (k % cols) * (w + pad)
+        sheet[y:y + h, x:x + w] = frames[k]
+    return sheet
+
+
+def save_gif(path, images, fps=30):
+    """An animated GIF of `images` -- a sequence (or an [T, h, w, 3] array / tensor) of uint8 RGB pictures of one size -- through PIL.
+    GIF keeps time in hundredths of a second: the frame duration is rounded to that."""
+    from PIL import Image
+    pics = [Image.fromarray(np.ascontiguousarray(im.cpu().numpy() if hasattr(im, "cpu") else im, dtype=np.uint8), "RGB") for im in images]
+    if not pics:
+        raise ValueError("save_gif: no images")
+    # (PIL folds a picture that is identical to its predecessor into it and adds up their durations: the clip plays the same)
+    pics[0].save(path, format="GIF", save_all=True, append_images=pics[1:], duration=max(10 * round(100 / fps), 10), loop=0, optimize=False)
+    return path

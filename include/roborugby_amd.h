@@ -350,6 +350,50 @@ int rr_policy_chase(rr_env *env, const float *obs, const int32_t *step_of, uint3
 int rr_render(rr_env *env, const int32_t *arenas, int32_t m, int32_t width, int32_t height, int32_t samples,
               uint8_t *rgb, void *stream);
 
+/* Egocentric pictures: one frame per (arena, robot), centred on the robot, its front up, coloured from its own side -- what a policy
+ * that drives ONE robot can look at (rr_render's frames are absolute in place, direction and team colour).  csrc/rr_render.hpp:
+ * k_render_ego.  An extension.
+ *
+ * Which arena and robot a frame shows.  Frame k shows arena arenas[k] (arenas == NULL: arena k) seen from robot robots[k], happy robots
+ * first (robots == NULL: robot 0).  Both are DEVICE pointers; duplicates and any order are allowed.
+ *
+ * Camera.  (cx, cy, rot) is the viewing robot's pose from the record, rounded to fp32; th = (360 - rot) * 0.017453292519943295f,
+ * c = cosf(th), s = sinf(th) -- exactly the values the draw list of rr_render holds for that robot.  The robot's front is its +u side
+ * (rr_render's convention); the front points UP in the frame, frame-right is the robot's +v side.
+ *
+ * Sample points.  All arithmetic is fp32; the three view constants are computed once on the host in double and then rounded:
+ *     f = (float)(span / (double)(width*S)),  hx = (float)(span * 0.5),  hy = (float)(span * 0.5 * height / width).
+ * Sample (a, b) of pixel (i, j), with S = `samples`, is
+ *     p = ((float)(i*S + a) + 0.5f) * f - hx          (to the right)
+ *     q = ((float)(j*S + b) + 0.5f) * f - hy          (downwards)
+ *     fwd = ahead - q
+ *     x = cx + (fwd*c - p*s),   y = cy + (fwd*s + p*c)
+ * The frame covers `span` arena units across and span*height/width down, both axes at the same scale; the robot's centre sits `ahead`
+ * units below the frame's centre (ahead > 0 looks further forward).  A frame with S samples at `width` decides the same sample points as
+ * a frame with 1 sample at width*S.
+ *
+ * Layers at (x, y): exactly rr_render's 1-4 -- background, goals, robots 0 .. NR-1, balls 0 .. NB-1, closed boundaries, the same inside
+ * tests; the viewing robot is drawn like any other -- and one new layer ON TOP: a sample with x < 0 || x > W || y < 0 || y > H is
+ * OUTSIDE, (96, 96, 96).  So the walls are visible, and a ball parked at x <= -1000 by goal scoring never shows.
+ *
+ * Colours with RR_EGO_RELATIVE: if the viewing robot is grumpy (index >= nr_happy) the palette is swapped pairwise -- the two team
+ * colours, the two ball colours, the two goal colours: blue robots and the blue goal are "mine", the green ball is "the one that scores
+ * for me", for either team.  For a happy viewer, or without the flag, the colours are rr_render's.
+ *
+ * The box filter for S > 1 is rr_render's.  rgb is [m, height, width, 3], with RR_EGO_PLANAR [m, 3, height, width]; every byte of the m
+ * frames is written on every call, and nothing beyond them.  A frame is written all zero if its arena index is outside 0 .. N-1, its
+ * robot index is outside 0 .. NR-1, or the viewing robot's pose is non-finite; such a value is never used as an index.
+ *
+ * Returns -1 (rr_last_error, "rr_render_ego: ...") and launches nothing for a null handle or rgb, m outside 1 .. 1 << 20, width outside
+ * 4 .. 1024 or not a multiple of 4, height outside 1 .. 1024, samples not 1, 2 or 4, span not finite or outside 16 .. 16384, ahead not
+ * finite or |ahead| > 8192, flag bits other than the two above, or an rgb that is not 4-byte aligned.  Accepted on every handle
+ * rr_render accepts (all dtypes, both libraries, one-shape libraries, budgeted handles: a parked arena shows its mid-step record);
+ * read-only on the records; launch-only: no allocation, no synchronisation. */
+#define RR_EGO_RELATIVE 1  /* colours from the viewing robot's side */
+#define RR_EGO_PLANAR   2  /* rgb is [m,3,height,width] instead of [m,height,width,3] */
+int rr_render_ego(rr_env *env, const int32_t *arenas, const int32_t *robots, int32_t m, int32_t width, int32_t height,
+                  int32_t samples, float span, float ahead, int32_t flags, uint8_t *rgb, void *stream);
+
 /* ---- config 5 (BASELINE.json): the learn step of the reference's DQN agent (Training_DQN_pytorch.py:25-67 DeepQNetwork
  * Linear 11 -> 256 -> 256 -> 8 + ReLU, MSELoss, Adam; :151-191 DQNAgent.learn) fused into two launches for the wide batches of the
  * batched trainer: forward of Q_eval(s) and Q_target(s'), TD target, loss gradient, backward and the weight-gradient reduction in

@@ -69,6 +69,7 @@ SYMBOLS = {
     "rr_hive_transition_held": (C.c_int, [_vp, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rr_hive_transition_held_f64": (C.c_int, [_vp, C.c_uint32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rr_render": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "rr_render_ego": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _vp, _vp]),
     "rr_track_prior_step": (C.c_int, [_vp, C.c_int32, _vp]),
     "rr_set_goal_scoring": (C.c_int, [_vp, C.c_int32, _vp]),
     "rr_goal_scores": (C.c_int, [_vp, _vp, _vp]),

@@ -1087,6 +1087,38 @@ int rr_render(rr_env *e, const int32_t *arenas, int32_t m, int32_t width, int32_
     });
 }
 
+// The same records seen from one robot per frame (rr_render.hpp: k_render_ego); the view's constants are computed here, once, in double.
+int rr_render_ego(rr_env *e, const int32_t *arenas, const int32_t *robots, int32_t m, int32_t width, int32_t height, int32_t samples,
+                  float span, float ahead, int32_t flags, uint8_t *rgb, void *stream) {
+    if (!e) return fail(-1, "rr_render_ego: null handle");
+    if (!rgb) return fail(-1, "rr_render_ego: null rgb");
+    if (m < 1 || m > (1 << 20)) return fail(-1, "rr_render_ego: between 1 and 1 << 20 frames");
+    if (width < 4 || width > 1024 || (width & 3)) return fail(-1, "rr_render_ego: width must be a multiple of 4 in 4 .. 1024 (four pixels per thread)");
+    if (height < 1 || height > 1024) return fail(-1, "rr_render_ego: height must be in 1 .. 1024");
+    if (samples != 1 && samples != 2 && samples != 4) return fail(-1, "rr_render_ego: samples must be 1, 2 or 4");
+    if (!(span >= 16.0f && span <= 16384.0f)) return fail(-1, "rr_render_ego: span must be finite, in 16 .. 16384 arena units");
+    if (!(ahead >= -8192.0f && ahead <= 8192.0f)) return fail(-1, "rr_render_ego: ahead must be finite, at most 8192 arena units either way");
+    if (flags & ~(RR_EGO_RELATIVE | RR_EGO_PLANAR)) return fail(-1, "rr_render_ego: unknown flag bits (RR_EGO_RELATIVE | RR_EGO_PLANAR)");
+    if ((uintptr_t)rgb & 3) return fail(-1, "rr_render_ego: rgb must be 4-byte aligned (the frames are stored as dwords)");
+    static_assert(RR_EGO_RELATIVE == RENDER_EGO_RELATIVE && RR_EGO_PLANAR == RENDER_EGO_PLANAR, "the header's flags are the kernel's");
+    return on_handle(e, "rr_render_ego", stream, [&](auto v) {
+        using C = typename decltype(v)::Cfg;
+        using L = RecLayout<C>;
+        static_assert(C::NR <= RENDER_MAX && C::NB <= RENDER_MAX && C::NR + C::NB <= RENDER_THREADS, "the draw list holds every entity");
+        const RenderLayout rl = { L::RCX, L::RCY, L::RROT, L::BCX, L::BCY, Arena<C>::P_STRIDE, C::NR, C::NRH, C::NB, C::NBP,
+                                  sizeof(typename C::Store) == 8 ? 1 : 0 };
+        const EgoView ev = render_ego_view(e->cfg.arena_w, e->cfg.arena_h, width, height, samples, span, ahead, flags);
+        const size_t quads = (size_t)width * (size_t)height / RENDER_QUAD;
+        const unsigned bx = (unsigned)((quads + RENDER_THREADS - 1) / RENDER_THREADS);
+        for (size_t f0 = 0; f0 < (size_t)m; f0 += 65535) {
+            const size_t nf = (size_t)m - f0 < 65535 ? (size_t)m - f0 : 65535;
+            hipLaunchKernelGGL(k_render_ego, dim3(bx, (unsigned)nf), dim3(RENDER_THREADS), 0, v.s, rl, ev, (const void *)v.recs(), v.n(), arenas,
+                               robots, f0, rgb);
+        }
+        return 0;
+    });
+}
+
 int rr_probe_hbm_copy(void *dst, const void *src, size_t bytes, void *stream) {
     if (!dst || !src || bytes < 16 || (bytes & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15))
         return fail(-1, "rr_probe_hbm_copy: 16-byte aligned buffers and a multiple of 16 bytes, please");

@@ -603,7 +603,7 @@ def train(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkp
 
 @torch.no_grad()
 def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, epsilon=0.2, preset="G", step_budget_clocks=0,
-              record=None, record_arenas=16, record_size=96, record_every=1):
+              record=None, record_arenas=16, record_size=96, record_every=1, record_view="field"):
     """A checkpoint written by train() plays the full game: the happy team is the hive (players.Hive: the reference's
     DQN_pytorch_player.Stephen -- one policy, one ball per robot), the grumpy team is OG_Twitchy, the line-up of the reference's
     main.py without its human.  Returns mean return per team over the steps played (per finished episode when any finished) and
@@ -612,7 +612,9 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
     that stepped an arena (neither re-placed nor NOT_READY), as in train().
     record: path of an animated GIF of the run -- after every `record_every`-th step one render_batch of the first `record_arenas` arenas,
     `record_size` pixels wide (a multiple of 4; the height keeps the arena's aspect); the frames stay on the device until the loop ends,
-    then one contact sheet per recorded step goes into the GIF.  None: nothing is rendered."""
+    then one contact sheet per recorded step goes into the GIF.  None: nothing is rendered.
+    record_view: "field" -- the whole arena --, or "ego": what the first hive robot of each recorded arena sees (render_ego: the robot
+    in the centre, its front up, 400 arena units across, `record_size` x `record_size` pixels)."""
     import roborugby_amd as rr
     from .env import STATUS_NOT_READY, STATUS_WAS_RESET
     from .players import Hive, og_twitchy
@@ -630,9 +632,13 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
     total_g = torch.zeros(num_envs, dtype=torch.float64, device=env.device)
     real_rows = torch.zeros((), dtype=torch.int64, device=env.device)
     parked_rows = torch.zeros((), dtype=torch.int64, device=env.device)
+    if record_view not in ("field", "ego"):
+        raise ValueError("play_hive(record_view=...): 'field' or 'ego'")
     if record is not None:
         rec_n, rec_every = min(int(record_arenas), num_envs), max(int(record_every), 1)
         rec_w, rec_h = int(record_size), max(int(round(record_size * p.arena_h / p.arena_w)), 1)
+        if record_view == "ego":
+            rec_h = rec_w
         rec_idx = torch.arange(rec_n, dtype=torch.int32, device=env.device)
         clip = torch.empty((len(range(rec_every - 1, steps, rec_every)), rec_n, rec_h, rec_w, 3), dtype=torch.uint8, device=env.device)
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -643,7 +649,10 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
         hive.act(out=thrust)
         _, reward, _, info = env.step_thrust(thrust)
         if record is not None and (k + 1) % rec_every == 0:
-            env.render_batch(rec_idx, rec_w, rec_h, out=clip[(k + 1) // rec_every - 1])
+            if record_view == "ego":
+                env.render_ego(rec_idx, int(hive.robots[0]), rec_w, rec_h, span=400.0, out=clip[(k + 1) // rec_every - 1])
+            else:
+                env.render_batch(rec_idx, rec_w, rec_h, out=clip[(k + 1) // rec_every - 1])
         if step_budget_clocks:  # (a NOT_READY row's reward is not written by the step)
             ready = (info.status & STATUS_NOT_READY) == 0
             total_h += torch.where(ready, reward, 0.0)
@@ -793,13 +802,15 @@ def main():
                     help="no training: the checkpoint's policy plays preset G as the happy team's hive mind against OG_Twitchy (--num-envs, --steps)")
     ap.add_argument("--record", default=None, metavar="GIF",
                     help="--play-hive: an animated GIF of the first 16 arenas (a contact sheet of 96-pixel frames per step), rendered on the device")
+    ap.add_argument("--record-view", default="field", choices=["field", "ego"],
+                    help="--record: the whole field of each arena, or what its first hive robot sees (robot in the centre, front up)")
     ap.add_argument("--train-hive", action="store_true",
                     help="train the hive mind in the full game (preset G): one transition per hive robot and step; --resume takes the agent of "
                          "any checkpoint, e.g. one trained in preset T (--num-envs, --steps, --checkpoint, --updates-per-step, --batch-size)")
     a = ap.parse_args()
     if a.play_hive:
         print(json.dumps(play_hive(a.play_hive, a.num_envs, a.steps, a.device, a.seed, preset=a.preset or "G", step_budget_clocks=a.budget,
-                                   record=a.record)))
+                                   record=a.record, record_view=a.record_view)))
         return
     if a.train_hive:
         print(json.dumps(train_hive(a.num_envs, a.steps, a.preset or "G", resume=a.resume, checkpoint=a.checkpoint,

@@ -9,6 +9,7 @@ memory + streams).  No CPU fallback exists: without the HIP library / a GPU this
 """
 import ctypes as C
 import math
+import numbers
 import types
 
 import numpy as np
@@ -555,6 +556,51 @@ class BatchedRoboRugbyEnv:
             raise ValueError(f"render_batch(out=...): a contiguous uint8 tensor of {m}x{h}x{w}x3 elements on {self.device}")
         _lib.check(self._lib.rr_render(self._h, _ptr(idx), m, w, h, int(samples), _ptr(out), self._stream()), "rr_render", self._lib)
         return out.view(m, h, w, 3)
+
+    def render_ego(self, arenas=None, robots=None, width=64, height=None, span=400.0, ahead=0.0, samples=1, relative=True, planar=False,
+                   out=None):
+        """Egocentric RGB frames, one per (arena, robot), in one launch, straight from the records on the device (rr_render_ego; the
+        picture is specified in include/roborugby_amd.h): -> uint8 [M, height, width, 3], or [M, 3, height, width] when `planar`, on the
+        env's device, enqueued on the current stream.  A frame is centred on its robot -- `ahead` arena units in front of it, when given --
+        with the robot's front up; it covers `span` arena units across, at the same scale downwards; beyond the walls it is grey.
+        relative: a grumpy viewer sees the team, ball and goal colours swapped, so that "mine" looks the same for either team.
+        arenas: as in render_batch (None: every arena).  robots: the viewing robot, happy robots first -- an int for every frame, or a
+        1-D int sequence / tensor of length M (None: robot 0); an index outside 0 .. NR-1 gives an all-zero frame, as does a viewer with a
+        non-finite pose.  height: None = width; width a multiple of 4.  out: a contiguous uint8 tensor of M * height * width * 3
+        elements on the device to write into.  Raises ValueError before any launch when the result would exceed 1 GiB."""
+        w = int(width)
+        h = w if height is None else int(height)
+
+        def index_list(x, name):
+            x = torch.as_tensor(x)
+            if x.is_floating_point() or x.dtype == torch.bool or x.dim() != 1:
+                raise ValueError(f"render_ego({name}=...): a 1-D sequence of integer indices")
+            return x.to(device=self.device, dtype=torch.int32).contiguous()
+
+        idx = None if arenas is None else index_list(arenas, "arenas")
+        m = self.num_envs if idx is None else int(idx.numel())
+        rob = None
+        if robots is not None:
+            if isinstance(robots, numbers.Integral) and not isinstance(robots, bool):
+                rob = torch.full((max(m, 1),), int(robots), dtype=torch.int32, device=self.device) if int(robots) != 0 else None
+            else:
+                rob = index_list(robots, "robots")
+                if int(rob.numel()) != m:
+                    raise ValueError(f"render_ego(robots=...): {int(rob.numel())} robots for {m} frames")
+        if m < 1 or w < 1 or h < 1:
+            raise ValueError("render_ego: at least one frame of at least one pixel")
+        if m * h * w * 3 > self.RENDER_BATCH_MAX_BYTES:
+            raise ValueError(f"render_ego: {m} frames of {w}x{h} are {m * h * w * 3 / 2 ** 30:.2f} GiB, above the 1 GiB a call may write; "
+                             "render fewer frames per call or smaller ones")
+        shape = (m, 3, h, w) if planar else (m, h, w, 3)
+        if out is None:
+            out = self._new(shape, torch.uint8)
+        elif not (out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == m * h * w * 3 and out.device == self.device):
+            raise ValueError(f"render_ego(out=...): a contiguous uint8 tensor of {m}x{h}x{w}x3 elements on {self.device}")
+        flags = (1 if relative else 0) | (2 if planar else 0)  # RR_EGO_RELATIVE, RR_EGO_PLANAR
+        _lib.check(self._lib.rr_render_ego(self._h, _ptr(idx), _ptr(rob), m, w, h, int(samples), float(span), float(ahead), flags, _ptr(out),
+                                           self._stream()), "rr_render_ego", self._lib)
+        return out.view(shape)
 
     def seed(self, seed=None):
         """Like the reference (RR_EnvBase.py:568-570) this does not re-seed placement; the reset RNG is keyed at

@@ -12,6 +12,7 @@ COLOR_BALL_POS = (80, 220, 100)
 COLOR_BALL_NEG = (60, 16, 83)
 COLOR_GOAL_HAPPY = (43, 146, 228)
 COLOR_GOAL_GRUMPY = (242, 53, 87)
+COLOR_OUTSIDE = (96, 96, 96)         # egocentric frames (BatchedRoboRugbyEnv.render_ego): beyond the walls
 COLOR_DASHBOARD_FILL = (200, 200, 200)
 DASHBOARD_WIDTH = 300
 

@@ -77,6 +77,26 @@ def score(pre, post, got, W, H):
     return q, e, ints
 
 
+BAR = 1e-5  # the north-star bar: fp32 positions within 1e-5
+
+
+def assert_distribution(tag, q, e, ints, done_ok):
+    """The bars an all-fp32 step is held to, from score()'s (quiet mask, per-arena error, integer-state equality) and done equality."""
+    c = ~q
+    assert q.sum() > 100 and c.sum() > 100, (tag, int(q.sum()), int(c.sum()))
+    assert done_ok.all(), tag
+    # quiet steps: the north-star bar, integer state exact
+    assert e[q].max() <= BAR, (tag, float(e[q].max()))
+    assert ints[q].all(), tag
+    # contact steps: the documented distribution
+    med, p90 = float(np.median(e[c])), float(np.percentile(e[c], 90))
+    flips = float((e[c] > 1e-2).mean())
+    assert med < 1e-5 and p90 < 3e-4 and flips < 0.025 and ints[c].mean() > 0.995, (tag, med, p90, flips, float(ints[c].mean()))
+    print(f"[{tag}] fp32 vs fp64: {int(q.sum())} quiet steps max rel err {e[q].max():.2e} (bar {BAR:g}); {int(c.sum())} contact steps "
+          f"median {med:.2e} p90 {p90:.2e} p99 {np.percentile(e[c], 99):.2e}, {100 * flips:.2f} % > 1e-2, integer state equal in "
+          f"{100 * ints[c].mean():.2f} %")
+
+
 def oracle_on_rounded_state(preset, pre, actions):
     """The fp64 oracle (= the reference's arithmetic, bit for bit on tests/golden) stepping every arena of `pre` ONCE from its state
     ROUNDED TO FP32, result rounded to fp32: what an ideal "fp32 state" implementation returns.  pre: robots [n,NR,10], robots_i,

@@ -15,7 +15,7 @@ import oracle_lib as ol
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-BAR = 1e-5
+BAR = fc.BAR
 
 
 def _env(preset, n, dtype="f32", **kw):
@@ -55,20 +55,7 @@ def _assert_state_mode(tag, q, e, ints, done_ok, pre, post, got, cfg):
         assert abs((e[c] > BAR).sum() - (e_o[c] > BAR).sum()) <= max(3, 0.02 * (e_o[c] > BAR).sum()), tag
 
 
-def _assert_distribution(tag, q, e, ints, done_ok):
-    c = ~q
-    assert q.sum() > 100 and c.sum() > 100, (tag, int(q.sum()), int(c.sum()))
-    assert done_ok.all(), tag
-    # quiet steps: the north-star bar, integer state exact
-    assert e[q].max() <= BAR, (tag, float(e[q].max()))
-    assert ints[q].all(), tag
-    # contact steps: the documented distribution
-    med, p90 = float(np.median(e[c])), float(np.percentile(e[c], 90))
-    flips = float((e[c] > 1e-2).mean())
-    assert med < 1e-5 and p90 < 3e-4 and flips < 0.025 and ints[c].mean() > 0.995, (tag, med, p90, flips, float(ints[c].mean()))
-    print(f"[{tag}] fp32 vs fp64: {int(q.sum())} quiet steps max rel err {e[q].max():.2e} (bar {BAR:g}); {int(c.sum())} contact steps "
-          f"median {med:.2e} p90 {p90:.2e} p99 {np.percentile(e[c], 99):.2e}, {100 * flips:.2f} % > 1e-2, integer state equal in "
-          f"{100 * ints[c].mean():.2f} %")
+_assert_distribution = fc.assert_distribution  # shared with the thrust entry and the host emulation: tests/fp32_checks.py
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f32_state"])

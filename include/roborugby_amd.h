@@ -45,7 +45,7 @@ extern "C" {
 #define RR_DTYPE_F32 1 /* state + arithmetic in fp32: the fast mode                                   */
 #define RR_DTYPE_F32_STATE 2 /* "fp32 state" (BASELINE config 2): the arenas' records in HBM are fp32, a step computes in fp64 between
                                 loading a record and writing it back -- one rounding per stored value and step, single-step results
-                                within 1e-5 of the fp64 reference on contact steps too.  Default lane widths, rr_step / rr_step_f64 /
+                                within 1e-5 of the fp64 reference on contact steps too.  The shape's lane width, rr_step / rr_step_f64 /
                                 rr_step_thrust(_f64) and every side entry; no rr_rollout, no step budget (both would keep unrounded
                                 state across steps) */
 

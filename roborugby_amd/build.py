@@ -24,22 +24,28 @@ LIB_EXACT = os.path.join(HERE, "libroborugby_amd_exact.so")
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 
-def header_config_table():
-    """(number of k_step translation units, entity counts of the built shapes) as csrc/rr_kstep.hpp states them: RR_KSTEP_PARTS and
-    the rows X(kind, part, NRH, NRG, NBP, NBN, precision, VW, DEF) of the product library's RR_CFG_TABLE.  KSTEP_PARTS and BUILT_SHAPES
-    must say the same (they are literals because an installed package may come without the sources): build_hip_library refuses to
-    compile otherwise, tests/test_abi_and_host.py checks it."""
+def header_config_rows():
+    """(RR_KSTEP_PARTS, the rows X(kind, part, NRH, NRG, NBP, NBN, precision, VW) of the product library's RR_CFG_TABLE as tuples of
+    (kind, part, nrh, nrg, nbp, nbn, lanes)) as csrc/rr_kstep.hpp states them"""
     with open(HDR_KSTEP) as f:
         text = f.read()
     parts = int(re.search(r"^#define RR_KSTEP_PARTS (\d+)$", text, re.M).group(1))
     table = re.search(r"^#else // the product library.*?^#endif", text, re.M | re.S).group(0)
-    rows = [tuple(int(v) for v in m.groups()) for m in re.finditer(r"X\((\d+), (\d+), (\d+), (\d+), (\d+), (\d+), \w+, \d+, [01]\)", table)]
+    rows = [tuple(int(v) for v in m.groups()) for m in re.finditer(r"X\((\d+), (\d+), (\d+), (\d+), (\d+), (\d+), \w+, (\d+)\)", table)]
     if not rows or sorted({r[1] for r in rows}) != list(range(parts)):
         raise RuntimeError("csrc/rr_kstep.hpp: the configuration table does not use every part 0..RR_KSTEP_PARTS-1")
-    return parts, {r[2:] for r in rows}
+    return parts, rows
 
 
-KSTEP_PARTS = 7
+def header_config_table():
+    """(number of k_step translation units, entity counts of the built shapes) as csrc/rr_kstep.hpp states them.  KSTEP_PARTS and
+    BUILT_SHAPES must say the same (they are literals because an installed package may come without the sources): build_hip_library
+    refuses to compile otherwise, tests/test_abi_and_host.py checks it."""
+    parts, rows = header_config_rows()
+    return parts, {r[2:6] for r in rows}
+
+
+KSTEP_PARTS = 4
 BUILT_SHAPES = {(1, 0, 1, 0), (2, 2, 4, 4), (1, 1, 1, 1)}  # (nrh, nrg, nbp, nbn) inside libroborugby_amd.so; any other: build_shape_library
 
 
@@ -73,7 +79,7 @@ def is_stale(exact=False):
 def build_hip_library(force=False, verbose=False, jobs=None, exact=False):
     """hipcc --offload-arch=gfx950 ... -> libroborugby_amd.so (cross-compiles without a GPU).
 
-    The step kernel's instantiations (14 configurations x up to five variants: most of the compile time) are compiled as
+    The step kernel's instantiations (nine configurations x up to five variants: most of the compile time) are compiled as
     KSTEP_PARTS objects next to the main translation unit, in parallel, and linked into the one shared library; no relocatable
     device code (every kernel is self-contained, csrc/rr_kstep.hpp).  RR_BUILD_JOBS / `jobs` bounds the parallelism."""
     lib_path = LIB_EXACT if exact else LIB

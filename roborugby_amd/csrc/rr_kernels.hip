@@ -1,10 +1,10 @@
 // rr_kernels.hip -- gfx950 kernels + the C-ABI (include/roborugby_amd.h) of the batched RoboRugby simulator.
 //
 // Launch geometry: 64-thread workgroups = 1 wavefront; a wavefront is cut into 64/VW virtual waves of VW
-// lanes and every virtual wave owns one arena (VW = 64: one wavefront per arena; VW = 16: four arenas per
-// wavefront, ...).  Each arena has a private LDS slice (Arena<C>) and never talks to another arena, so there
+// lanes and every virtual wave owns one arena (the built widths: G 8 lanes = eight arenas per wavefront, D 4 = sixteen,
+// T 2 = thirty-two).  Each arena has a private LDS slice (Arena<C>) and never talks to another arena, so there
 // is no workgroup barrier anywhere and no inter-workgroup traffic -- any blockIdx -> XCD placement is equally
-// good (arenas share nothing, there is no L2 reuse to protect).  65,536 arenas = 2,048..65,536 workgroups.
+// good (arenas share nothing, there is no L2 reuse to protect).  65,536 arenas = 2,048..8,192 workgroups.
 //
 // HBM layout: one record per arena -- the persistent reals (Arena::P) with the int32 bookkeeping (Arena::I) right behind
 // them, padded to a 64-B multiple (G/fp64: 960 B, T/fp64: 256 B).  Inside a record the fields are entity-minor (SoA over
@@ -320,35 +320,22 @@ __global__ void k_observe_kind(SimParams<typename C::Real> sp, const typename C:
 // arena and the observation of every hive robot with its own ball, in one launch.  Read-only on the records.
 // (launch bounds as k_step's: the registers of as many waves as the LDS slices admit -- left alone, the serial observer of kind 1 takes
 // the whole file and halves the occupancy)
-template <class C, typename O, int KIND>
+// HELD (rr_hive_observe_held, under the budgeted step; rr_hive.hpp: "held rows"): an arena parked mid-step keeps its assign / obs rows --
+// they belong to the step it is in the middle of -- and says so in held[arena]; every other arena is observed exactly as without HELD
+// (`held` is not read then).  The return is per virtual wave, where the `arena >= n` one sits: nothing below exchanges data with the lanes
+// of another arena (vw_argmin's butterfly has width VW, RR_VOTE takes the group's share of the ballot, the LDS slice is the arena's own).
+template <class C, typename O, int KIND, bool HELD>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void k_hive(SimParams<typename C::Real> sp, const typename C::Store *recs,
                                                               const int32_t *irecs, int n, uint32_t robot_mask, int32_t *assign,
-                                                              O *obs) {
-    __shared__ Arena<C> lds[arenas_per_block<C>()];
-    const int wave = threadIdx.x / C::VW; // virtual wave = arena slot in this workgroup
-    const int arena = blockIdx.x * arenas_per_block<C>() + wave;
-    if (arena >= n || wave >= arenas_per_block<C>()) return;
-    Arena<C> &A = lds[wave];
-    const typename C::Store *rec = recs + (size_t)arena * Arena<C>::P_STRIDE;
-    load_record(A, rec, irecs + (size_t)arena * Arena<C>::I_STRIDE);
-    if (KIND == OBS_V2) derive(A, sp);
-    Rec<C> q = { rec };
-    hive_observe<C, O, KIND>(A, q, sp, robot_mask, assign + (size_t)arena * C::NR, obs + (size_t)arena * C::NR * 11);
-}
-// The same under the budgeted step (rr_hive.hpp: "held rows"): an arena parked mid-step keeps its assign / obs rows -- they belong to the
-// step it is in the middle of -- and says so in held[arena]; every other arena is observed exactly as k_hive does it.  The return is per
-// virtual wave, where the `arena >= n` one sits: nothing below exchanges data with the lanes of another arena (vw_argmin's butterfly has
-// width VW, RR_VOTE takes the group's share of the ballot, the LDS slice is the arena's own).
-template <class C, typename O, int KIND>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void k_hive_held(SimParams<typename C::Real> sp, const typename C::Store *recs,
-                                                                   const int32_t *irecs, int n, uint32_t robot_mask, int32_t *assign,
-                                                                   O *obs, uint8_t *held) {
+                                                              O *obs, uint8_t *held) {
     __shared__ Arena<C> lds[arenas_per_block<C>()];
     const int wave = threadIdx.x / C::VW; // virtual wave = arena slot in this workgroup
     const int arena = blockIdx.x * arenas_per_block<C>() + wave;
     if (arena >= n || wave >= arenas_per_block<C>()) return;
     const int32_t *irec = irecs + (size_t)arena * Arena<C>::I_STRIDE;
-    if (hive_hold<C>(irec, held + arena)) return;
+    if constexpr (HELD) {
+        if (hive_hold<C>(irec, held + arena)) return;
+    }
     Arena<C> &A = lds[wave];
     const typename C::Store *rec = recs + (size_t)arena * Arena<C>::P_STRIDE;
     load_record(A, rec, irec);
@@ -469,8 +456,8 @@ template <> const SimParams<float> &params_of<float>(const rr_env *e) { return e
 
 // calls f(Cfg<...>{}) for the configuration the handle was created with
 template <class F> static int dispatch(const rr_env *e, F &&f) {
-#define X(kind_, part_, a, b, c, d, R_, vw_, def_) \
-    if (e->kind == kind_ && e->vw == vw_) return f(Cfg<a, b, c, d, R_, vw_>{});
+#define X(kind_, part_, a, b, c, d, R_, vw_) \
+    if (e->kind == kind_) return f(Cfg<a, b, c, d, R_, vw_>{});
     RR_CFG_TABLE(X)
 #undef X
     return fail(-1, "corrupt handle");
@@ -535,7 +522,7 @@ int rr_create(const rr_config *cfg, rr_env **out) {
     if (cfg->struct_size != (int32_t)sizeof(rr_config)) return fail(-1, "rr_create: rr_config.struct_size mismatch");
     if (cfg->num_envs <= 0) return fail(-1, "rr_create: num_envs must be positive");
     int shape = -1; // of the first row of the table with these entity counts
-#define X(kind_, part_, a, b, c, d, R_, vw_, def_) \
+#define X(kind_, part_, a, b, c, d, R_, vw_) \
     if (shape < 0 && cfg->nr_happy == a && cfg->nr_grumpy == b && cfg->nb_pos == c && cfg->nb_neg == d) shape = kind_ % RR_NUM_SHAPES;
     RR_CFG_TABLE(X)
 #undef X
@@ -561,12 +548,6 @@ int rr_create(const rr_config *cfg, rr_env **out) {
     e->cfg = *cfg;
     e->kind = shape + RR_NUM_SHAPES * cfg->dtype;
     e->prog.n = 3; e->prog.id[0] = KEEPER_NAUGHTY; e->prog.id[1] = KEEPER_CHASE; e->prog.id[2] = KEEPER_PUSHPOS;
-    const char *want = getenv("RR_VW");
-    const int want_vw = want ? atoi(want) : 0;
-#define X(kind_, part_, a, b, c, d, R_, vw_, def_) \
-    if (e->kind == kind_ && (e->vw == 0 || want_vw == vw_)) e->vw = vw_;
-    RR_CFG_TABLE(X)
-#undef X
     fill_params(e->spd, *cfg);
     fill_params(e->spf, *cfg);
     size_t pstride = 0, preals = 0, snapw = 0, isnapw = 0;
@@ -574,6 +555,7 @@ int rr_create(const rr_config *cfg, rr_env **out) {
     const size_t rsz = cfg->dtype == RR_DTYPE_F64 ? 8 : 4; // bytes per STORED real (the record)
     dispatch(e, [&](auto c) {
         using CC = decltype(c);
+        e->vw = CC::VW;
         pstride = Arena<CC>::P_STRIDE; preals = Arena<CC>::P_REALS; snapw = Arena<CC>::SNAP_WORDS; isnapw = Arena<CC>::ISNAP_WORDS;
         apb = arenas_per_block<CC>();
         return 0;
@@ -676,8 +658,8 @@ static int step_impl(rr_env *e, const int32_t *actions, const float *thrust, int
         } else {
             if (nsteps == 1 && e->park) step(k_step<C, O, false, true>, 1, 0, e->park, e->budget);
             else if (nsteps == 1) step(k_step<C, O, false>, 1, 0, nullptr, 0);
-            else if constexpr (std::is_same<O, float>::value && default_width<C>()) step(k_step<C, O, true>, nsteps, repeat, nullptr, 0); // (build time)
-            else return fail(-1, "rr_rollout: built for float outputs and the default lane widths (RR_VW unset) only");
+            else if constexpr (std::is_same<O, float>::value) step(k_step<C, O, true>, nsteps, repeat, nullptr, 0); // (build time)
+            else return fail(-1, "rr_rollout: float outputs only");
         }
         if (e->order) hipLaunchKernelGGL(k_order, dim3(1), dim3(ORDER_THREADS), 0, v.s, (const uint32_t *)e->cost, e->order, e->ngroups);
         if (extras) v.per_thread(k_extras_end<C, O>, v.sp(), v.recs(), n, v.xs(), e->prog, e->custom_prog ? 1 : 0, reward, reward_g, status, done);
@@ -900,18 +882,16 @@ static int check_hive_args(rr_env *e, bool pointers, uint32_t robot_mask, int32_
     if (nr < 32 && (robot_mask >> nr)) return fail(-1, who + ": robot mask has a bit at or above the number of robots");
     return 0;
 }
-// held != null: rr_hive_observe_held (k_hive_held)
+// want_held: rr_hive_observe_held (k_hive<..., HELD = true>)
 template <typename O>
 static int hive_observe_impl(rr_env *e, uint32_t robot_mask, int32_t kind, int32_t *assign, O *obs, uint8_t *held, bool want_held, void *stream) {
     const char *who = want_held ? "rr_hive_observe_held" : "rr_hive_observe";
     if (int rc = check_hive_args(e, assign && obs && (held || !want_held), robot_mask, kind, who)) return rc;
     return on_handle<O>(e, who, stream, [&](auto v) {
         using C = typename decltype(v)::Cfg;
-        if (want_held)
-            v.per_wave(kind == OBS_V2 ? k_hive_held<C, O, OBS_V2> : k_hive_held<C, O, OBS_V1>, v.sp(), v.recs(), v.irecs(), v.n(), robot_mask,
-                       assign, obs, held);
-        else
-            v.per_wave(kind == OBS_V2 ? k_hive<C, O, OBS_V2> : k_hive<C, O, OBS_V1>, v.sp(), v.recs(), v.irecs(), v.n(), robot_mask, assign, obs);
+        auto launch = [&](auto kernel) { v.per_wave(kernel, v.sp(), v.recs(), v.irecs(), v.n(), robot_mask, assign, obs, held); };
+        if (want_held) launch(kind == OBS_V2 ? k_hive<C, O, OBS_V2, true> : k_hive<C, O, OBS_V1, true>);
+        else launch(kind == OBS_V2 ? k_hive<C, O, OBS_V2, false> : k_hive<C, O, OBS_V1, false>);
         return 0;
     }, want_held ? "rr_hive_observe_held_f64: handle was created with RR_DTYPE_F32" : "rr_hive_observe_f64: handle was created with RR_DTYPE_F32");
 }
@@ -1060,6 +1040,22 @@ int rr_policy_chase(rr_env *e, const float *obs, const int32_t *step_of, uint32_
 
 // Pictures (rr_render.hpp): one kernel for every configuration -- the record's layout travels as a runtime struct, filled here where the
 // handle's configuration is known.  Frames in blockIdx.y, at most 65,535 per launch.
+extern "C++" {
+template <class C> static RenderLayout render_layout() {
+    using L = RecLayout<C>;
+    static_assert(C::NR <= RENDER_MAX && C::NB <= RENDER_MAX && C::NR + C::NB <= RENDER_THREADS, "the draw list holds every entity");
+    return { L::RCX, L::RCY, L::RROT, L::BCX, L::BCY, Arena<C>::P_STRIDE, C::NR, C::NRH, C::NB, C::NBP, sizeof(typename C::Store) == 8 ? 1 : 0 };
+}
+// launch(grid, f0) renders frames f0 .. f0 + grid.y - 1 of the m asked for, four pixels per thread
+template <class F> static void render_chunks(int32_t m, int32_t width, int32_t height, F &&launch) {
+    const size_t quads = (size_t)width * (size_t)height / RENDER_QUAD;
+    const unsigned bx = (unsigned)((quads + RENDER_THREADS - 1) / RENDER_THREADS);
+    for (size_t f0 = 0; f0 < (size_t)m; f0 += 65535) {
+        const size_t nf = (size_t)m - f0 < 65535 ? (size_t)m - f0 : 65535;
+        launch(dim3(bx, (unsigned)nf), f0);
+    }
+}
+} // extern "C++"
 int rr_render(rr_env *e, const int32_t *arenas, int32_t m, int32_t width, int32_t height, int32_t samples, uint8_t *rgb, void *stream) {
     if (!e) return fail(-1, "rr_render: null handle");
     if (!rgb) return fail(-1, "rr_render: null rgb");
@@ -1069,20 +1065,13 @@ int rr_render(rr_env *e, const int32_t *arenas, int32_t m, int32_t width, int32_
     if (samples != 1 && samples != 2 && samples != 4) return fail(-1, "rr_render: samples must be 1, 2 or 4");
     if ((uintptr_t)rgb & 3) return fail(-1, "rr_render: rgb must be 4-byte aligned (the frames are stored as dwords)");
     return on_handle(e, "rr_render", stream, [&](auto v) {
-        using C = typename decltype(v)::Cfg;
-        using L = RecLayout<C>;
-        static_assert(C::NR <= RENDER_MAX && C::NB <= RENDER_MAX && C::NR + C::NB <= RENDER_THREADS, "the draw list holds every entity");
-        const RenderLayout rl = { L::RCX, L::RCY, L::RROT, L::BCX, L::BCY, Arena<C>::P_STRIDE, C::NR, C::NRH, C::NB, C::NBP,
-                                  sizeof(typename C::Store) == 8 ? 1 : 0 };
+        const RenderLayout rl = render_layout<typename decltype(v)::Cfg>();
         const double W = e->cfg.arena_w, H = e->cfg.arena_h;
         const RenderView rv = { (float)W, (float)H, (float)(W / (double)(width * samples)), (float)(H / (double)(height * samples)),
                                 width, height, samples };
-        const size_t quads = (size_t)width * (size_t)height / RENDER_QUAD;
-        const unsigned bx = (unsigned)((quads + RENDER_THREADS - 1) / RENDER_THREADS);
-        for (size_t f0 = 0; f0 < (size_t)m; f0 += 65535) {
-            const size_t nf = (size_t)m - f0 < 65535 ? (size_t)m - f0 : 65535;
-            hipLaunchKernelGGL(k_render, dim3(bx, (unsigned)nf), dim3(RENDER_THREADS), 0, v.s, rl, rv, (const void *)v.recs(), v.n(), arenas, f0, rgb);
-        }
+        render_chunks(m, width, height, [&](dim3 grid, size_t f0) {
+            hipLaunchKernelGGL(k_render, grid, dim3(RENDER_THREADS), 0, v.s, rl, rv, (const void *)v.recs(), v.n(), arenas, f0, rgb);
+        });
         return 0;
     });
 }
@@ -1102,19 +1091,11 @@ int rr_render_ego(rr_env *e, const int32_t *arenas, const int32_t *robots, int32
     if ((uintptr_t)rgb & 3) return fail(-1, "rr_render_ego: rgb must be 4-byte aligned (the frames are stored as dwords)");
     static_assert(RR_EGO_RELATIVE == RENDER_EGO_RELATIVE && RR_EGO_PLANAR == RENDER_EGO_PLANAR, "the header's flags are the kernel's");
     return on_handle(e, "rr_render_ego", stream, [&](auto v) {
-        using C = typename decltype(v)::Cfg;
-        using L = RecLayout<C>;
-        static_assert(C::NR <= RENDER_MAX && C::NB <= RENDER_MAX && C::NR + C::NB <= RENDER_THREADS, "the draw list holds every entity");
-        const RenderLayout rl = { L::RCX, L::RCY, L::RROT, L::BCX, L::BCY, Arena<C>::P_STRIDE, C::NR, C::NRH, C::NB, C::NBP,
-                                  sizeof(typename C::Store) == 8 ? 1 : 0 };
+        const RenderLayout rl = render_layout<typename decltype(v)::Cfg>();
         const EgoView ev = render_ego_view(e->cfg.arena_w, e->cfg.arena_h, width, height, samples, span, ahead, flags);
-        const size_t quads = (size_t)width * (size_t)height / RENDER_QUAD;
-        const unsigned bx = (unsigned)((quads + RENDER_THREADS - 1) / RENDER_THREADS);
-        for (size_t f0 = 0; f0 < (size_t)m; f0 += 65535) {
-            const size_t nf = (size_t)m - f0 < 65535 ? (size_t)m - f0 : 65535;
-            hipLaunchKernelGGL(k_render_ego, dim3(bx, (unsigned)nf), dim3(RENDER_THREADS), 0, v.s, rl, ev, (const void *)v.recs(), v.n(), arenas,
-                               robots, f0, rgb);
-        }
+        render_chunks(m, width, height, [&](dim3 grid, size_t f0) {
+            hipLaunchKernelGGL(k_render_ego, grid, dim3(RENDER_THREADS), 0, v.s, rl, ev, (const void *)v.recs(), v.n(), arenas, robots, f0, rgb);
+        });
         return 0;
     });
 }

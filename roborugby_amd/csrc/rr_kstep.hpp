@@ -1,7 +1,7 @@
 // rr_kstep.hpp -- the step kernel template (k_step) and the table of built configurations.
 //
 // Shared by rr_kernels.hip (the C-ABI + every other kernel) and rr_kstep_inst.hip: the product build compiles the k_step
-// instantiations -- 14 configurations x up to five variants, most of the library's compile time -- in parallel translation
+// instantiations -- nine configurations x up to five variants, most of the library's compile time -- in parallel translation
 // units (rr_kstep_inst.hip with -DRR_PART=k holds the explicit instantiations of its share, rr_kernels.hip declares them
 // `extern template` under -DRR_SPLIT_BUILD).  No relocatable device code is involved: every kernel is self-contained, each
 // object registers its own code object, the host side only needs the launch stubs at link time.  Tuning builds
@@ -131,55 +131,53 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
 #endif
 }
 
-// Built configurations, one row each: X(kind, part, NRH, NRG, NBP, NBN, precision, VW, DEF)
+// Built configurations, one row each: X(kind, part, NRH, NRG, NBP, NBN, precision, VW)
 //   kind      = shape + RR_NUM_SHAPES * dtype -- shapes: 0 = T (1+0 robots, 1+0 balls), 1 = G (2+2, 4+4), 2 = D (1+1, 1+1: the two-team duel);
 //               dtype 0: fp64, 1: fp32, 2: fp32 state with fp64 arithmetic (rr_sim.hpp: F32State)
 //   part      = the translation unit of the split build (rr_kstep_inst.hip -DRR_PART=part) that holds the row's k_step instantiations:
-//               G kernels are the slow ones to compile, so they are spread first
+//               no two G rows share a part (the G and D kernels are the slow ones to compile); the parts are balanced so that each
+//               compiles in less time than rr_kernels.hip itself, which bounds the build (measured at 8 jobs: profiles/one_width/)
 //   precision = double | float | F32State; it also decides which k_step variants exist (RR_KSTEP_INST_<precision> below)
-//   VW        = lanes per arena.  The first VW listed for a kind is the one a handle gets; the environment variable RR_VW selects
-//               another built width (kernel tuning / A-B runs)
-//   DEF       = 1: rr_rollout's multi-step variant is built for this row (the default width of its kind)
+//   VW        = lanes per arena: one width per kind (T 2, G 8, D 4), the one every handle of that kind gets.  Other widths are
+//               measured with tuning builds (RR_TUNE_VW_* below), never carried by the product library
 // Everything else -- dispatch, the shapes rr_create recognises, the extern declarations and the explicit instantiations of the split
 // build, roborugby_amd/build.py's KSTEP_PARTS and BUILT_SHAPES -- is derived from these rows.
-#define RR_KSTEP_PARTS 7
+#define RR_KSTEP_PARTS 4
 #if defined(RR_CUSTOM_SHAPE)
 // A library for ONE shape outside the built list (roborugby_amd.build.build_shape_library: the reference's entity counts are free
 // integers, RR_Constants.py:30-34): -DRR_CUSTOM_SHAPE -DRR_NRH= -DRR_NRG= -DRR_NBP= -DRR_NBN= -DRR_CVW=<lanes per arena> (+ RR_CFG_SUBSET:
 // one translation unit, implicit instantiation).  Precisions: fp64 and fp32 state / fp64 arithmetic.
-#define RR_CFG_TABLE(X) X(0, 0, RR_NRH, RR_NRG, RR_NBP, RR_NBN, double, RR_CVW, 1) X(6, 0, RR_NRH, RR_NRG, RR_NBP, RR_NBN, F32State, RR_CVW, 1)
-#elif defined(RR_CFG_SUBSET) && RR_CFG_SUBSET == 2 // occupancy probe: T at 4 lanes per arena (its LDS admits 4 waves per SIMD)
-#define RR_CFG_TABLE(X) X(0, 0, 1, 0, 1, 0, double, 4, 0) X(1, 0, 2, 2, 4, 4, double, 8, 1)
-#elif defined(RR_CFG_SUBSET) && RR_CFG_SUBSET == 3 // tuning builds of the duel shape
-#define RR_CFG_TABLE(X) X(2, 0, 1, 1, 1, 1, double, 4, 1) X(1, 0, 2, 2, 4, 4, double, 8, 1)
-#elif defined(RR_CFG_SUBSET) // tuning builds only (tools/build_variant.sh): the two default configurations, quick to compile
-#define RR_CFG_TABLE(X) X(0, 0, 1, 0, 1, 0, double, 2, 1) X(1, 0, 2, 2, 4, 4, double, 8, 1)
+#define RR_CFG_TABLE(X) X(0, 0, RR_NRH, RR_NRG, RR_NBP, RR_NBN, double, RR_CVW) X(6, 0, RR_NRH, RR_NRG, RR_NBP, RR_NBN, F32State, RR_CVW)
+#elif defined(RR_CFG_SUBSET)
+// Tuning builds only (tools/build_variant.sh, tools/kernel_resources.py): T and G in fp64, quick to compile, at -DRR_TUNE_VW_T=<lanes> /
+// -DRR_TUNE_VW_G=<lanes> per arena (default: the product's widths); -DRR_TUNE_VW_D=<lanes> adds the duel shape (the product's: 4).
+#ifndef RR_TUNE_VW_T
+#define RR_TUNE_VW_T 2
+#endif
+#ifndef RR_TUNE_VW_G
+#define RR_TUNE_VW_G 8
+#endif
+#ifdef RR_TUNE_VW_D
+#define RR_TUNE_ROW_D(X) X(2, 0, 1, 1, 1, 1, double, RR_TUNE_VW_D)
+#else
+#define RR_TUNE_ROW_D(X)
+#endif
+#define RR_CFG_TABLE(X) X(0, 0, 1, 0, 1, 0, double, RR_TUNE_VW_T) X(1, 0, 2, 2, 4, 4, double, RR_TUNE_VW_G) RR_TUNE_ROW_D(X)
 #else // the product library (roborugby_amd/build.py reads the rows between this line and the #endif)
-#define RR_CFG_TABLE(X)                                                                                                                    \
-    X(0, 5, 1, 0, 1, 0, double, 2, 1) X(0, 5, 1, 0, 1, 0, double, 4, 0) X(0, 6, 1, 0, 1, 0, double, 8, 0) X(0, 6, 1, 0, 1, 0, double, 64, 0)     \
-    X(1, 0, 2, 2, 4, 4, double, 8, 1) X(1, 1, 2, 2, 4, 4, double, 16, 0) X(1, 2, 2, 2, 4, 4, double, 32, 0) X(1, 3, 2, 2, 4, 4, double, 64, 0)   \
-    X(2, 1, 1, 1, 1, 1, double, 4, 1) X(2, 2, 1, 1, 1, 1, double, 8, 0) X(2, 3, 1, 1, 1, 1, double, 64, 0)                                    \
-    X(3, 6, 1, 0, 1, 0, float, 2, 1) X(3, 6, 1, 0, 1, 0, float, 4, 0) X(3, 6, 1, 0, 1, 0, float, 64, 0)                                       \
-    X(4, 4, 2, 2, 4, 4, float, 8, 1) X(4, 4, 2, 2, 4, 4, float, 16, 0) X(4, 5, 2, 2, 4, 4, float, 64, 0)                                      \
-    X(5, 0, 1, 1, 1, 1, float, 4, 1)                                                                                                      \
-    X(6, 5, 1, 0, 1, 0, F32State, 2, 1) X(7, 2, 2, 2, 4, 4, F32State, 8, 1) X(8, 6, 1, 1, 1, 1, F32State, 4, 1)
+#define RR_CFG_TABLE(X)                                                                                                 \
+    X(0, 1, 1, 0, 1, 0, double, 2) X(1, 0, 2, 2, 4, 4, double, 8) X(2, 3, 1, 1, 1, 1, double, 4)                         \
+    X(3, 0, 1, 0, 1, 0, float, 2) X(4, 1, 2, 2, 4, 4, float, 8) X(5, 2, 1, 1, 1, 1, float, 4)                            \
+    X(6, 3, 1, 0, 1, 0, F32State, 2) X(7, 2, 2, 2, 4, 4, F32State, 8) X(8, 2, 1, 1, 1, 1, F32State, 4)
 #endif
 constexpr int RR_NUM_SHAPES = 3;
-#define X(kind_, part_, a, b, c, d, R_, vw_, def_) static_assert(part_ >= 0 && part_ < RR_KSTEP_PARTS && kind_ >= 0 && kind_ < 3 * RR_NUM_SHAPES, "row");
+#define X(kind_, part_, a, b, c, d, R_, vw_) static_assert(part_ >= 0 && part_ < RR_KSTEP_PARTS && kind_ >= 0 && kind_ < 3 * RR_NUM_SHAPES, "row");
 RR_CFG_TABLE(X)
 #undef X
-// is C's lane width the default of its kind (DEF: the widths rr_rollout's multi-step variant is built for)?
-template <class C> constexpr bool default_width() {
-#define X(kind_, part_, a, b, c, d, R_, vw_, def_) if (std::is_same<C, Cfg<a, b, c, d, R_, vw_>>::value) return def_ != 0;
-    RR_CFG_TABLE(X)
-#undef X
-    return false;
-}
 
 // ---- the k_step instantiations of a row: PREFIX = `extern` declares them (rr_kernels.hip under -DRR_SPLIT_BUILD: they live in
 // rr_kstep_inst.hip's objects), empty defines them (rr_kstep_inst.hip).  Exactly what step_impl can launch for the row:
-//   double  : plain + budgeted for float and double outputs, and (DEF) rr_rollout's multi-step loop for float outputs
-//   float   : plain + budgeted and (DEF) multi-step, float outputs only
+//   double  : plain + budgeted for float and double outputs, and rr_rollout's multi-step loop for float outputs
+//   float   : plain + budgeted + multi-step, float outputs only
 //   F32State: the plain single-step kernel only, float and double outputs
 #define RR_KSTEP_SIG(C_, O_)                                                                                                       \
     (SimParams<typename C_::Real>, typename C_::Store *, int32_t *, int, const int32_t *, const float *, int, O_ *, O_ *, uint8_t *, \
@@ -188,18 +186,20 @@ template <class C> constexpr bool default_width() {
 #define RR_KSTEP_ONE(PREFIX, a, b, c, d, R_, vw_, O_, MULTI_, BUDGET_) \
     PREFIX template __global__ void k_step<Cfg<a, b, c, d, R_, vw_>, O_, MULTI_, BUDGET_> RR_KSTEP_SIG(RR_KSTEP_CFG(a, b, c, d, R_, vw_), O_);
 #define RR_KSTEP_PLAIN(PREFIX, a, b, c, d, R_, vw_, O_) RR_KSTEP_ONE(PREFIX, a, b, c, d, R_, vw_, O_, false, false)
-#define RR_KSTEP_MULTI_0(PREFIX, a, b, c, d, R_, vw_, O_)
-#define RR_KSTEP_MULTI_1(PREFIX, a, b, c, d, R_, vw_, O_) RR_KSTEP_ONE(PREFIX, a, b, c, d, R_, vw_, O_, true, false)
-#define RR_KSTEP_VARIANTS(PREFIX, a, b, c, d, R_, vw_, O_, MULTI_) \
-    RR_KSTEP_PLAIN(PREFIX, a, b, c, d, R_, vw_, O_) RR_KSTEP_ONE(PREFIX, a, b, c, d, R_, vw_, O_, false, true) RR_KSTEP_MULTI_##MULTI_(PREFIX, a, b, c, d, R_, vw_, O_)
-#define RR_KSTEP_INST_double(PREFIX, a, b, c, d, vw_, def_) \
-    RR_KSTEP_VARIANTS(PREFIX, a, b, c, d, double, vw_, float, def_) RR_KSTEP_VARIANTS(PREFIX, a, b, c, d, double, vw_, double, 0)
-#define RR_KSTEP_INST_float(PREFIX, a, b, c, d, vw_, def_) RR_KSTEP_VARIANTS(PREFIX, a, b, c, d, float, vw_, float, def_)
-#define RR_KSTEP_INST_F32State(PREFIX, a, b, c, d, vw_, def_) \
+#define RR_KSTEP_BUDGET(PREFIX, a, b, c, d, R_, vw_, O_) RR_KSTEP_ONE(PREFIX, a, b, c, d, R_, vw_, O_, false, true)
+#define RR_KSTEP_MULTI(PREFIX, a, b, c, d, R_, vw_, O_) RR_KSTEP_ONE(PREFIX, a, b, c, d, R_, vw_, O_, true, false)
+#define RR_KSTEP_INST_double(PREFIX, a, b, c, d, vw_)                                                                                   \
+    RR_KSTEP_PLAIN(PREFIX, a, b, c, d, double, vw_, float) RR_KSTEP_BUDGET(PREFIX, a, b, c, d, double, vw_, float)                      \
+    RR_KSTEP_MULTI(PREFIX, a, b, c, d, double, vw_, float)                                                                              \
+    RR_KSTEP_PLAIN(PREFIX, a, b, c, d, double, vw_, double) RR_KSTEP_BUDGET(PREFIX, a, b, c, d, double, vw_, double)
+#define RR_KSTEP_INST_float(PREFIX, a, b, c, d, vw_)                                                                                    \
+    RR_KSTEP_PLAIN(PREFIX, a, b, c, d, float, vw_, float) RR_KSTEP_BUDGET(PREFIX, a, b, c, d, float, vw_, float)                        \
+    RR_KSTEP_MULTI(PREFIX, a, b, c, d, float, vw_, float)
+#define RR_KSTEP_INST_F32State(PREFIX, a, b, c, d, vw_) \
     RR_KSTEP_PLAIN(PREFIX, a, b, c, d, F32State, vw_, float) RR_KSTEP_PLAIN(PREFIX, a, b, c, d, F32State, vw_, double)
 
 #if defined(RR_SPLIT_BUILD) && !defined(RR_CFG_SUBSET)
-#define X(kind_, part_, a, b, c, d, R_, vw_, def_) RR_KSTEP_INST_##R_(extern, a, b, c, d, vw_, def_)
+#define X(kind_, part_, a, b, c, d, R_, vw_) RR_KSTEP_INST_##R_(extern, a, b, c, d, vw_)
 RR_CFG_TABLE(X)
 #undef X
 #endif

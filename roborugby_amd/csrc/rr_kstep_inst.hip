@@ -12,9 +12,6 @@
 #define RR_IF_PART_1(...)
 #define RR_IF_PART_2(...)
 #define RR_IF_PART_3(...)
-#define RR_IF_PART_4(...)
-#define RR_IF_PART_5(...)
-#define RR_IF_PART_6(...)
 #if RR_PART == 0
 #undef RR_IF_PART_0
 #define RR_IF_PART_0(...) __VA_ARGS__
@@ -27,19 +24,10 @@
 #elif RR_PART == 3
 #undef RR_IF_PART_3
 #define RR_IF_PART_3(...) __VA_ARGS__
-#elif RR_PART == 4
-#undef RR_IF_PART_4
-#define RR_IF_PART_4(...) __VA_ARGS__
-#elif RR_PART == 5
-#undef RR_IF_PART_5
-#define RR_IF_PART_5(...) __VA_ARGS__
-#elif RR_PART == 6
-#undef RR_IF_PART_6
-#define RR_IF_PART_6(...) __VA_ARGS__
 #else
 #error "RR_PART out of range"
 #endif
 
-#define X(kind_, part_, a, b, c, d, R_, vw_, def_) RR_IF_PART_##part_(RR_KSTEP_INST_##R_(RR_NOTHING, a, b, c, d, vw_, def_))
+#define X(kind_, part_, a, b, c, d, R_, vw_) RR_IF_PART_##part_(RR_KSTEP_INST_##R_(RR_NOTHING, a, b, c, d, vw_))
 RR_CFG_TABLE(X)
 #undef X

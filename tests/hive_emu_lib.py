@@ -13,7 +13,7 @@ SO = os.path.join(HERE, "emu", "librr_hive_emu.so")
 CSRC = os.path.join(ol.REPO, "roborugby_amd", "csrc")
 SRC = [os.path.join(HERE, "emu", "rr_hive_emu.cpp")] + [os.path.join(CSRC, f) for f in ("rr_hive.hpp", "rr_extras.hpp", "rr_sim.hpp")]
 PRESET_ID = {"T": 0, "G": 1, "D": 2, "X": 3}
-# lanes per arena the emulation is built for: the product's widths (csrc/rr_kstep.hpp; X: build.shape_lanes) and 64
+# lanes per arena the emulation is built for: the product's width of the shape (csrc/rr_kstep.hpp; X: build.shape_lanes), wider groups and 64
 LANES = {"T": (2, 4, 64), "G": (8, 16, 32, 64), "D": (4, 64), "X": (8, 64)}
 for _wide, _shape in ol.SHAPE.items():  # the non-square ids run their shape's build at their own W, H
     PRESET_ID[_wide], LANES[_wide] = PRESET_ID[_shape], LANES[_shape]

@@ -39,6 +39,17 @@ def test_build_constants_match_the_configuration_table():
     parts, shapes = build.header_config_table()
     assert parts == build.KSTEP_PARTS
     assert shapes == build.BUILT_SHAPES and (2, 2, 4, 4) in shapes
+    # one row, so one lane width, per kind (shape + 3 * dtype; shapes T, G, D): T 2, G 8, D 4 lanes in all three precisions
+    _, rows = build.header_config_rows()
+    assert sorted(r[0] for r in rows) == list(range(9))
+    assert {r[0]: r[6] for r in rows} == {kind: (2, 8, 4)[kind % 3] for kind in range(9)}
+    assert {r[0] % 3: r[2:6] for r in rows} == {0: (1, 0, 1, 0), 1: (2, 2, 4, 4), 2: (1, 1, 1, 1)}
+    # ... and nothing a user loads or includes selects another: the environment switch for it is gone
+    for top in ("roborugby_amd", "include"):
+        for root, _, files in os.walk(os.path.join(REPO, top)):
+            for f in files:
+                if f.endswith((".py", ".hip", ".hpp", ".h", ".cpp")):
+                    assert "RR_VW" not in open(os.path.join(root, f), errors="ignore").read(), f
 
 
 def test_config_struct_matches_header_layout():

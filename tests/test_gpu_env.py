@@ -283,3 +283,45 @@ def test_abi_rejects_misuse_without_crashing():
     # bad actions are a per-arena status, not an error: the arena keeps its previous thrust (KeyError in the reference)
     obs, rew, done, info = env.step(torch.full((8,), 9, dtype=torch.int32, device="cuda"))
     assert bool(((info.status & 128) != 0).all())
+
+
+def _same_bits(x, y):
+    if x is None or y is None:
+        return x is None and y is None
+    if x.is_floating_point():
+        return bool((torch.isnan(x) == torch.isnan(y)).all()) and torch.equal(torch.nan_to_num(x), torch.nan_to_num(y))
+    return torch.equal(x, y)
+
+
+def test_one_lane_width_per_kind_whatever_the_environment_says(monkeypatch):
+    """The library carries one lane width per shape and precision (T 2, G 8, D 4); the retired RR_VW switch selects nothing.  33 arenas
+    leave a partial last group at 32, 8 and 16 arenas per wavefront: a handle created with RR_VW=64 in the environment reports the
+    same lanes and takes a step bit-identically to one created without it."""
+    rr = _rr()
+    n = 33
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(17)
+    for preset, lanes in (("T", 2), ("G", 8), ("D", 4)):
+        acts = torch.randint(0, 8, (n, rr.PRESETS[preset].nr), generator=gen, device="cuda", dtype=torch.int32)
+        monkeypatch.delenv("RR_VW", raising=False)
+        seed_env = rr.BatchedRoboRugbyEnv(n, preset=preset, seed=31, time_limit=False, auto_reset=False)
+        seed_env.reset()
+        st = seed_env.get_state()
+        seed_env.close()
+        for dtype in ("f64", "f32", "f32_state"):
+            got = []
+            for vw in (None, "64"):
+                if vw:
+                    monkeypatch.setenv("RR_VW", vw)
+                else:
+                    monkeypatch.delenv("RR_VW", raising=False)
+                env = rr.BatchedRoboRugbyEnv(n, preset=preset, seed=31, time_limit=False, auto_reset=False, dtype=dtype)
+                assert env.lanes_per_env() == lanes, (preset, dtype, vw)
+                env.set_state(st["robots"], st["robots_i"], st["balls"], st["step"])
+                obs, rew, done, info = env.step(acts)
+                post = env.get_state()
+                got.append([obs, rew, done, info.adblGrumpyState, info.dblGrumpyScore, info.status] + [post[k] for k in sorted(post)])
+                env.close()
+            assert len(got[0]) == len(got[1]) == 10
+            for k, (x, y) in enumerate(zip(*got)):
+                assert _same_bits(x, y), (preset, dtype, k)

@@ -1,6 +1,6 @@
 """Latency of ONE pathological arena (tools/fixtures/squeezed_G.npz: a ball squeezed between two robots -- every
 sub-step runs the push, all 10 resolve passes and the undo loop) -- the floor under any launch that contains it.
-usage: [RR_LIB_PATH=...] [RR_VW=..] python tools/slow_arena_bench.py [n_copies]"""
+usage: [RR_LIB_PATH=...] python tools/slow_arena_bench.py [n_copies]"""
 import os, sys, numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -441,6 +441,28 @@ int rr_dqn_store(rr_dqn *dqn, const float *state, const int32_t *action, const f
 /* Adam moments (same order as rr_dqn_grads) and step count out of / into the handle: checkpoint / resume. */
 int rr_dqn_adam_state(rr_dqn *dqn, float *exp_avg, float *exp_avg_sq, int64_t *step, int32_t set, void *stream);
 
+/* ---- the pixel agent's choose_action (roborugby_amd/csrc/rr_cnn.hip; roborugby_amd/dqn.py PixelQNetwork / PixelDQNAgent): the forward of
+ * the fixed convolutional Q network over n rows of planar uint8 pixels [n, channels, 64, 64] (PixelObservation(size=64, stack=1..4):
+ * channels = 3 * stack), argmax and the epsilon-greedy draw, on the bf16 matrix cores.
+ *   conv1 8x8, stride 4, no padding, ReLU: weight [16, channels, 8, 8], bias [16] -> [16, 15, 15]
+ *   conv2 4x4, stride 2, no padding, ReLU: weight [32, 16, 4, 4],       bias [32] -> [32, 6, 6], flattened (c, y, x) to 1152
+ *   fc1, ReLU: [256, 1152], [256];   fc2: [8, 256], [8] -> 8 Q-values
+ * params = these eight tensors in that order (torch.nn layouts, fp32), read as they stand at call time: nothing is kept from one call
+ * to the next (the first call allocates 635 KB of scratch in the handle, every call rewrites it; calls on one handle must be ordered,
+ * e.g. on one stream).  The network's input is pixel * 2^-8 (not / 255).
+ * THE ARITHMETIC (this is the specification; tests/cnn_ref.py is it in numpy):
+ *   - in all four layers both operands of every product are bf16: a pixel's integer value 0..255 (exact in bf16), a weight rounded to
+ *     nearest-even from the fp32 parameter, a hidden activation rounded to nearest-even after bias and ReLU;
+ *   - the products are summed in fp32, in no particular order;
+ *   - conv1's sum times 2^-8 (exact), every bias add and ReLU are fp32; the Q-values are the fp32 sums plus the fp32 bias.
+ * actions[i] = the FIRST maximum of row i's Q-values, or with probability epsilon a uniform action: exactly rr_dqn_act's draw
+ * (Philox4x32-10 of (seed, row, call), u <= epsilon, then word 1 & 7).  qvalues [n, 8] is optional (NULL: not written).
+ * n: 1 .. 1<<22, any value (a last partial tile is masked: no row >= n is read or written).  pixels: contiguous, 16-byte aligned.
+ * Returns -1 (message: rr_dqn_last_error) and launches nothing for a null handle / params entry / pixels / actions, channels outside
+ * {3, 6, 9, 12}, n out of range, an epsilon that is NaN or outside [0, 1], a misaligned pixels.  Parameters must be finite. */
+int rr_cnn_act(rr_dqn *dqn, const float *const params[8], const uint8_t *pixels, int32_t n, int32_t channels, float epsilon,
+               uint64_t seed, uint32_t call, int32_t *actions, float *qvalues, void *stream);
+
 /* Introspection used by bench.py for the roofline line: bytes of the per-arena HBM record, and how many lanes of
  * a wavefront work on one arena (64 = one wavefront per arena; smaller = several arenas packed per wavefront). */
 int rr_state_bytes_per_env(const rr_env *env, int64_t *bytes);

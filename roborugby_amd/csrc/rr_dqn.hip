@@ -25,6 +25,7 @@
 #include <string>
 
 #include "../../include/roborugby_amd.h"
+#include "rr_dqn_shared.hpp"
 
 namespace {
 
@@ -289,14 +290,6 @@ __global__ __launch_bounds__(NT, 1) void k_dqn_fwd_bwd(Net ev, Net tg, Batch bt,
 // DQNAgent.choose_action (Training_DQN_pytorch.py:138-149) for a whole batch of observations in ONE launch: the same tiled forward
 // as the learn step, argmax over the eight Q values (first maximum, like torch.argmax), and the epsilon-greedy draw from a
 // counter-based generator keyed by (seed, row, call counter).
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 __global__ __launch_bounds__(NT, 1) void k_dqn_act(Net ev, const float *obs, int n, float epsilon, uint64_t seed, uint32_t call,
                                                    int32_t *actions, float *qvalues) {
     __shared__ float X0[H * LDX], X1[H * LDX], S[12 * LDX], Q[NA * TM];
@@ -316,12 +309,7 @@ __global__ __launch_bounds__(NT, 1) void k_dqn_act(Net ev, const float *obs, int
             float mx = Q[t];
 #pragma unroll
             for (int a = 1; a < NA; a++) { const float q = Q[a * TM + t]; if (q > mx) { mx = q; best = a; } }
-            if (epsilon > 0.0f) {
-                uint32_t r[4] = { (uint32_t)row, call, 0x0AC7u, 0u };
-                philox4x32_10(r, (uint32_t)seed, (uint32_t)(seed >> 32));
-                if ((float)r[0] * 2.3283064365386963e-10f <= epsilon) best = (int)(r[1] & 7u); // np.random.random() <= epsilon: explore
-            }
-            actions[row] = best;
+            actions[row] = epsilon_greedy(best, row, call, seed, epsilon);
             if (qvalues) {
 #pragma unroll
                 for (int a = 0; a < NA; a++) qvalues[(size_t)row * NA + a] = Q[a * TM + t];
@@ -422,13 +410,7 @@ int dfail(int code, const char *msg) { g_dqn_err = msg; return code; }
 
 } // namespace
 
-struct rr_dqn {
-    int device, nwg;
-    float *partials, *m1, *m2;
-    long long step;
-    uint32_t *chunk_off; // rr_dqn_store's per-chunk offsets (grown on demand; a call with a larger batch than any before allocates)
-    size_t chunk_cap;
-};
+int rr_dqn_fail(int code, const char *msg) { return dfail(code, msg); }
 
 extern "C" {
 
@@ -448,7 +430,7 @@ int rr_dqn_create(int32_t device, rr_dqn **out) {
     { const char *w = getenv("RR_DQN_WGS"); const int k = w ? atoi(w) : 0; if (k > 0 && k < cus) cus = k; }
     rr_dqn *d = new rr_dqn();
     d->device = device; d->nwg = cus; d->step = 0; d->partials = nullptr; d->m1 = nullptr; d->m2 = nullptr;
-    d->chunk_off = nullptr; d->chunk_cap = 0;
+    d->chunk_off = nullptr; d->chunk_cap = 0; d->cnn_weights = nullptr;
     hipError_t e = hipMalloc((void **)&d->partials, sizeof(float) * (size_t)P_STRIDE * (size_t)d->nwg);
     if (e == hipSuccess) e = hipMalloc((void **)&d->m1, sizeof(float) * P_STRIDE);
     if (e == hipSuccess) e = hipMalloc((void **)&d->m2, sizeof(float) * P_STRIDE);
@@ -470,6 +452,7 @@ int rr_dqn_destroy(rr_dqn *d) {
     if (!d) return 0;
     (void)hipFree(d->partials); (void)hipFree(d->m1); (void)hipFree(d->m2);
     if (d->chunk_off) (void)hipFree(d->chunk_off);
+    if (d->cnn_weights) (void)hipFree(d->cnn_weights);
     delete d;
     return 0;
 }

@@ -440,6 +440,188 @@ class BatchedDQNAgent:
             self.eps_dec = eps_dec_override
 
 
+class PixelQNetwork(nn.Module):
+    """The fixed convolutional Q network of the pixel agent (include/roborugby_amd.h: rr_cnn_act): uint8 [n, C, 64, 64] -> conv 8x8 / 4 (16)
+    -> conv 4x4 / 2 (32) -> 1152 -> 256 -> n_actions, ReLU between.  The input is pixel * 2^-8 (not / 255): exact in every precision."""
+
+    def __init__(self, channels, n_actions=8):
+        super().__init__()
+        self.conv1 = nn.Conv2d(channels, 16, 8, stride=4)
+        self.conv2 = nn.Conv2d(16, 32, 4, stride=2)
+        self.fc1 = nn.Linear(32 * 6 * 6, 256)
+        self.fc2 = nn.Linear(256, n_actions)
+
+    def forward(self, x):
+        x = x.to(self.conv1.weight.dtype) * (1 / 256)
+        x = F.relu(self.conv1(x))
+        x = F.relu(self.conv2(x))
+        x = F.relu(self.fc1(x.flatten(1)))
+        return self.fc2(x)
+
+
+class PixelDQNAgent:
+    """BatchedDQNAgent's surface on the pixels of PixelObservation(size=64, stack=channels / 3).  Acting -- every row, every step -- is
+    rr_cnn_act (one HIP kernel on the bf16 matrix cores, csrc/rr_cnn.hip) where it applies: on the GPU, contiguous uint8 rows, channels
+    in {3, 6, 9, 12}, 8 actions; anything else, and fused=False, goes through the torch module.  Learning is PyTorch autograd on the same
+    parameters (MSE on r + gamma max Q_target, Adam, target sync and the epsilon schedule as in BatchedDQNAgent), the replay ring holds
+    uint8 frames and is written with torch indexing: 2 * channels * 4096 + 13 bytes per transition."""
+    FUSED_CHANNELS = (3, 6, 9, 12)
+
+    def __init__(self, channels=12, gamma=.99, epsilon=1.0, lr=.0005, batch_size=256, n_actions=8, max_mem_size=65536, eps_end=0.2,
+                 eps_dec=.999997, target_update_freq=100000, device="cpu", seed=0, fused=None):
+        self.channels, self.gamma, self.epsilon, self.eps_end, self.eps_dec = int(channels), gamma, epsilon, eps_end, eps_dec
+        self.n_actions, self.mem_size, self.batch_size = n_actions, int(max_mem_size), int(batch_size)
+        self.target_update_freq = int(target_update_freq)
+        self.device = torch.device(device)
+        self.mem_cntr, self._eps_cntr, self._next_target_sync = 0, 0, self.target_update_freq
+        self.target_syncs, self.updates, self.last_loss = 0, 0, None
+        self.gen = torch.Generator(device=self.device)
+        self.gen.manual_seed(seed)
+        self._seed = int(seed)
+        torch.manual_seed(seed)
+        self.Q_eval = PixelQNetwork(self.channels, n_actions).to(self.device)
+        self.Q_target = copy.deepcopy(self.Q_eval)
+        self.optimizer = torch.optim.Adam(self.Q_eval.parameters(), lr=lr)
+        m, d, shape = self.mem_size, self.device, (self.channels, 64, 64)
+        self.state_memory = torch.zeros((m,) + shape, dtype=torch.uint8, device=d)
+        self.new_state_memory = torch.zeros((m,) + shape, dtype=torch.uint8, device=d)
+        self.action_memory = torch.zeros(m, dtype=torch.int64, device=d)
+        self.reward_memory = torch.zeros(m, dtype=torch.float32, device=d)
+        self.terminal_memory = torch.zeros(m, dtype=torch.bool, device=d)
+        can_fuse = self.device.type == "cuda" and self.channels in self.FUSED_CHANNELS and n_actions == 8
+        self.fused = can_fuse if fused is None else bool(fused)
+        if self.fused and not can_fuse:
+            raise ValueError("fused=True needs a GPU, 3 / 6 / 9 / 12 channels and 8 actions")
+        self._fused_h = None
+        if self.fused:
+            from . import _lib
+            self._rrlib = _lib.load()
+            h = C.c_void_p()
+            _lib.check_dqn(self._rrlib.rr_dqn_create(self.device.index or 0, C.byref(h)), "rr_dqn_create", self._rrlib)
+            self._fused_h = h
+        self._act_calls = 0  # choose_action calls so far: keys the kernel's epsilon draws (checkpointed)
+
+    def close(self):
+        h, self._fused_h = getattr(self, "_fused_h", None), None
+        if h:
+            self._rrlib.rr_dqn_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _rows(self, pixels):
+        if pixels.dim() == 5:  # PixelObservation with several robots: [N, R, C, 64, 64], a row per (arena, robot)
+            pixels = pixels.reshape(-1, *pixels.shape[2:])
+        if pixels.dim() != 4 or tuple(pixels.shape[1:]) != (self.channels, 64, 64):
+            raise ValueError(f"pixels: [n, {self.channels}, 64, 64] or [N, R, {self.channels}, 64, 64], not {tuple(pixels.shape)}")
+        return pixels
+
+    @torch.no_grad()
+    def choose_action(self, pixels, epsilon_override=None, qvalues=None):
+        """[n, C, 64, 64] (or [N, R, C, 64, 64]) -> int32 [n]: epsilon-greedy per row.  qvalues: a float32 [n, 8] tensor the fused path
+        fills with the Q-values it acted on (None: not written)."""
+        eps = self.epsilon if epsilon_override is None else epsilon_override
+        pixels = self._rows(pixels)
+        n = pixels.shape[0]
+        if (self.fused and pixels.dtype == torch.uint8 and pixels.is_contiguous() and pixels.data_ptr() % 16 == 0 and 1 <= n <= 1 << 22
+                and pixels.device == self.Q_eval.fc2.weight.device):
+            return self._act_fused(pixels, eps, qvalues)
+        q = self.Q_eval(pixels)
+        if qvalues is not None:
+            qvalues.copy_(q)
+        greedy = q.argmax(dim=1)
+        if eps <= 0:
+            return greedy.to(torch.int32)
+        rand = torch.randint(0, self.n_actions, (n,), generator=self.gen, device=self.device)
+        explore = torch.rand(n, generator=self.gen, device=self.device) <= eps
+        return torch.where(explore, rand, greedy).to(torch.int32)
+
+    def _act_fused(self, pixels, eps, qvalues=None):
+        from . import _lib
+        n = pixels.shape[0]
+        out = torch.empty(n, dtype=torch.int32, device=self.device)
+        params = list(self.Q_eval.parameters())
+        assert all(p.is_contiguous() and p.dtype == torch.float32 for p in params)
+        if qvalues is not None:
+            assert qvalues.dtype == torch.float32 and qvalues.is_contiguous() and tuple(qvalues.shape) == (n, 8)
+        ptrs = (C.c_void_p * 8)(*[p.data_ptr() for p in params])
+        self._act_calls += 1
+        _lib.check_dqn(self._rrlib.rr_cnn_act(self._fused_h, C.byref(ptrs), C.c_void_p(pixels.data_ptr()), n, self.channels,
+                                              float(min(max(eps, 0.0), 1.0)), int(self._seed), self._act_calls & 0xFFFFFFFF,
+                                              C.c_void_p(out.data_ptr()), C.c_void_p(qvalues.data_ptr()) if qvalues is not None else None,
+                                              C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "rr_cnn_act", self._rrlib)
+        return out
+
+    @torch.no_grad()
+    def store_transition(self, state, action, reward, state_, done, valid=None):
+        """Appends the rows with valid=True (None: all) to the ring, in row order"""
+        state, state_ = self._rows(state), self._rows(state_)
+        if valid is not None:
+            idx = valid.reshape(-1).nonzero(as_tuple=True)[0]
+            state, action, reward, state_, done = state[idx], action.reshape(-1)[idx], reward.reshape(-1)[idx], state_[idx], done.reshape(-1)[idx]
+        n = state.shape[0]
+        if n == 0:
+            return
+        if n > self.mem_size:
+            raise ValueError(f"{n} transitions in one call do not fit a replay ring of {self.mem_size}")
+        pos = (self.mem_cntr + torch.arange(n, device=self.device)) % self.mem_size
+        self.state_memory[pos] = state.to(torch.uint8)
+        self.new_state_memory[pos] = state_.to(torch.uint8)
+        self.action_memory[pos] = action.reshape(-1).long()
+        self.reward_memory[pos] = reward.reshape(-1).float()
+        self.terminal_memory[pos] = done.reshape(-1).bool()
+        self.mem_cntr += n
+
+    def learn(self):
+        """One gradient step on batch_size sampled transitions + the per-transition schedules (BatchedDQNAgent.learn)"""
+        if self.mem_cntr < self.batch_size:
+            return None
+        max_mem = min(self.mem_size, self.mem_cntr)
+        batch = torch.randperm(max_mem, generator=self.gen, device=self.device)[:self.batch_size]
+        self.optimizer.zero_grad(set_to_none=False)
+        q_eval = self.Q_eval(self.state_memory[batch]).gather(1, self.action_memory[batch].view(-1, 1)).squeeze(1)
+        with torch.no_grad():
+            q_next = self.Q_target(self.new_state_memory[batch]).masked_fill(self.terminal_memory[batch].view(-1, 1), 0.0)
+            q_target = self.reward_memory[batch] + self.gamma * q_next.max(dim=1)[0]
+        loss = F.mse_loss(q_eval, q_target)
+        loss.backward()
+        self.optimizer.step()
+        self.updates += 1
+        if self.mem_cntr >= self._next_target_sync:
+            with torch.no_grad():
+                for pt, pe in zip(self.Q_target.parameters(), self.Q_eval.parameters()):
+                    pt.copy_(pe)
+            self._next_target_sync = (self.mem_cntr // self.target_update_freq + 1) * self.target_update_freq
+            self.target_syncs += 1
+        n_new = self.mem_cntr - self._eps_cntr
+        if n_new > 0:
+            self.epsilon = max(self.epsilon * math.pow(self.eps_dec, n_new), self.eps_end)
+            self._eps_cntr = self.mem_cntr
+        self.last_loss = loss.detach()
+        return self.last_loss
+
+    def state_dict(self):
+        """the agent without its replay (as BatchedDQNAgent's)"""
+        return dict(kind="pixel", channels=self.channels, q_eval=self.Q_eval.state_dict(), q_target=self.Q_target.state_dict(),
+                    optimizer=self.optimizer.state_dict(), epsilon=self.epsilon, mem_cntr=self.mem_cntr, updates=self.updates,
+                    target_syncs=self.target_syncs, act_calls=self._act_calls, fused=self.fused)
+
+    def load_state_dict(self, sd):
+        if sd.get("kind") != "pixel" or int(sd["channels"]) != self.channels:
+            raise ValueError(f"not a checkpoint of a pixel agent with {self.channels} channels")
+        self.Q_eval.load_state_dict(sd["q_eval"])
+        self.Q_target.load_state_dict(sd["q_target"])
+        self.optimizer.load_state_dict(sd["optimizer"])
+        self._act_calls = int(sd.get("act_calls", 0))
+        self.epsilon = sd["epsilon"]
+        self.updates, self.target_syncs = sd.get("updates", 0), sd.get("target_syncs", 0)
+        self._eps_cntr = self.mem_cntr  # (the replay is not checkpointed: the schedules are re-anchored as in BatchedDQNAgent)
+        self._next_target_sync = (self.mem_cntr // self.target_update_freq + 1) * self.target_update_freq
+
+
 @torch.no_grad()
 def evaluate(env, policy, episodes=1):
     """Mean return per episode of `policy(obs) -> int32 [N]` over every arena of `env` (auto-reset env, time_limit rule):
@@ -778,6 +960,84 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
     return res
 
 
+def train_pixels(num_envs=4096, steps=300, stack=4, span=400.0, mem_size=65536, device="cuda:0", seed=0, checkpoint=None, resume=None,
+                 log_every=50, learn=True, updates_per_step=1, batch_size=256, dtype="f64", eps_dec=.999997, eps_end=0.2,
+                 target_sync_vector_steps=64, out=None, step_budget_clocks=0, fused=None):
+    """train()'s loop on pixels: preset T seen through PixelObservation(env, robots=0, size=64, stack=stack, span=span), the agent a
+    PixelDQNAgent.  Per vector step, serial on one stream: choose_action (rr_cnn_act: one launch for every arena) -> env.step + the new
+    frames -> store_transition of the rows that were transitions (not re-placements, as in train()) -> updates_per_step x learn()
+    (PyTorch autograd).  Returns train()'s result dict (+ stack, span, fused_act, loss).
+    The replay ring holds both observations of a transition as uint8 frames: 2 * 3 * stack * 4096 bytes = 96 KB per transition at
+    stack 4, 6.4 GB at the default mem_size of 65,536 (24 KB and 1.6 GB at stack 1).  The observation before the step is copied once per
+    step (PixelObservation overwrites its buffer): num_envs * 48 KB at stack 4.
+    The budgeted step is not wired to pixels: step_budget_clocks != 0 is refused."""
+    import roborugby_amd as rr
+    from .pixels import PixelObservation
+    if step_budget_clocks:
+        raise ValueError("train_pixels: the budgeted step (step_budget_clocks) is not supported on pixel observations; use 0")
+    if not 1 <= int(stack) <= 4:
+        raise ValueError("train_pixels: stack in 1..4 (the network takes 3, 6, 9 or 12 channels)")
+    env = rr.make("RoboRugbySimpleDuel-v3", num_envs=num_envs, preset="T", device=device, seed=seed, dtype=dtype)
+    B = int(batch_size)
+    agent = PixelDQNAgent(channels=3 * int(stack), batch_size=B, n_actions=env.action_space.n, device=device, seed=seed,
+                          max_mem_size=mem_size, target_update_freq=max(100000, target_sync_vector_steps * num_envs),
+                          eps_dec=eps_dec, eps_end=eps_end, fused=fused)
+    view = PixelObservation(env, robots=0, size=64, stack=int(stack), span=span)
+    if resume:
+        ck = torch.load(resume, map_location=device)
+        agent.load_state_dict(ck["agent"])
+        env.load_checkpoint_state(ck)
+        pixels = view.restart()  # the frames are not checkpointed: every stack starts over from the restored state
+    else:
+        pixels = view.reset()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    score_sum = torch.zeros(num_envs, device=device)
+    real_rows = torch.zeros((), dtype=torch.int64, device=device)
+    before = torch.empty_like(pixels)
+    for i in range(steps):
+        action = agent.choose_action(pixels)
+        before.copy_(pixels)
+        pixels, reward, done, info = view.step(action.view(-1, 1))
+        real = (info.status & (1024 | 16384)) == 0  # a call that only re-placed the arena is not a transition
+        score_sum += reward
+        real_rows += real.sum()
+        if learn:
+            agent.store_transition(before, action, reward, pixels, done, valid=real)
+            for _ in range(updates_per_step):
+                agent.learn()
+        if log_every and (i + 1) % log_every == 0:
+            torch.cuda.synchronize()
+            lr_, _, ll, cnt = env.episode_stats()
+            fin = cnt > 0
+            avg = float(lr_[fin].mean()) if bool(fin.any()) else float("nan")
+            print(f"step {i + 1} epsilon {agent.epsilon:.6f} updates {agent.updates} target-syncs {agent.target_syncs} finished-episodes "
+                  f"{int(cnt.sum())} avg-last-return {avg:.1f} loss {float(agent.last_loss) if agent.last_loss is not None else float('nan'):.4f}",
+                  flush=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if checkpoint:
+        os.makedirs(os.path.dirname(os.path.abspath(checkpoint)), exist_ok=True)
+        torch.save(dict(agent=agent.state_dict(), **env.checkpoint_state()), checkpoint)
+    lr_, _, ll, cnt = env.episode_stats()
+    n_real = int(real_rows.item())
+    res = dict(env_steps_per_sec=num_envs * steps / dt, seconds=dt, num_envs=num_envs, steps=steps, transitions=n_real,
+               step_budget_clocks=0, learn_calls=agent.updates, updates_per_step=updates_per_step if learn else 0, batch_size=B,
+               samples_per_transition=(updates_per_step * B / num_envs) if learn else 0.0, overlap_learn=False,
+               replay_transitions=agent.mem_size, target_update_freq=agent.target_update_freq, target_syncs=agent.target_syncs,
+               epsilon=agent.epsilon, eps_dec=eps_dec, eps_end=eps_end, finished_episodes=int(cnt.sum()), fused_learn_step=False,
+               mean_step_reward=float(score_sum.mean() / max(steps, 1)), preset="T", dtype=dtype, curve=[],
+               stack=int(stack), span=float(span), fused_act=bool(agent.fused),
+               loss=float(agent.last_loss) if agent.last_loss is not None else None)
+    agent.close()
+    env.close()
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)) or ".", exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-envs", type=int, default=65536)
@@ -807,7 +1067,18 @@ def main():
     ap.add_argument("--train-hive", action="store_true",
                     help="train the hive mind in the full game (preset G): one transition per hive robot and step; --resume takes the agent of "
                          "any checkpoint, e.g. one trained in preset T (--num-envs, --steps, --checkpoint, --updates-per-step, --batch-size)")
+    ap.add_argument("--train-pixels", action="store_true",
+                    help="train the convolutional agent on preset T's egocentric 64 x 64 frames (PixelObservation); acting is rr_cnn_act "
+                         "(--num-envs, default 4096 here; --steps, --checkpoint, --resume, --updates-per-step, --batch-size, --pixel-stack)")
+    ap.add_argument("--pixel-stack", type=int, default=4, help="--train-pixels: frames per observation (1..4; 3 channels each)")
     a = ap.parse_args()
+    if a.train_pixels:
+        envs = a.num_envs if a.num_envs != ap.get_default("num_envs") else 4096  # (an observation is 48 KB at stack 4, not 44 bytes)
+        res = train_pixels(envs, a.steps, a.pixel_stack, device=a.device, seed=a.seed, checkpoint=a.checkpoint, resume=a.resume,
+                           log_every=a.log_every, learn=not a.no_learn, updates_per_step=a.updates_per_step, batch_size=a.batch_size or 256,
+                           eps_dec=a.eps_dec, out=a.out, step_budget_clocks=a.budget, fused=False if a.no_fused else None)
+        print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
+        return
     if a.play_hive:
         print(json.dumps(play_hive(a.play_hive, a.num_envs, a.steps, a.device, a.seed, preset=a.preset or "G", step_budget_clocks=a.budget,
                                    record=a.record, record_view=a.record_view)))

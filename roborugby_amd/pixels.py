@@ -62,6 +62,10 @@ class PixelObservation:
         self._buf.copy_(nxt)
         return self._pixels()
 
+    def restart(self):
+        """every stack starts over from the state the env is in now (after load_checkpoint_state / set_state: the frames are not part of it)"""
+        return self._update(None, None)
+
     def reset(self, mask=None):
         self.lidar = self.env.reset(mask)
         if mask is None:

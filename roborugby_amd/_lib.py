@@ -181,3 +181,41 @@ def check(rc, what, lib=None, err_fn="rr_last_error"):
 
 def check_dqn(rc, what, lib):
     check(rc, what, lib, "rr_dqn_last_error")
+
+
+class DqnHandle:
+    """Owner of one rr_dqn handle (rr_dqn_create .. rr_dqn_destroy): the per-workgroup partial gradients and the Adam moments of the fused
+    learn step, ~73 MB of device memory.  `h` is the handle (None once closed), `lib` the library it lives in."""
+
+    def __init__(self, device):
+        self.device, self.lib, self.h = device, load(), None
+        h = C.c_void_p()
+        check_dqn(self.lib.rr_dqn_create(device.index or 0, C.byref(h)), "rr_dqn_create", self.lib)
+        self.h = h
+
+    def close(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            self.lib.rr_dqn_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stream(self):
+        """the device's current torch stream, as the C-ABI takes it"""
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def call(self, name, *args):
+        """lib.<name>(handle, *args), an RRError with rr_dqn_last_error's message unless it returns 0"""
+        check_dqn(getattr(self.lib, name)(self.h, *args), name, self.lib)
+
+    def act(self, params, obs, n, epsilon, seed, calls, actions, q=None, stream=None):
+        """rr_dqn_act on the 11-256-256-8 network `params` (its six tensors): epsilon-greedy int32 actions for the n rows of `obs`, the
+        draws keyed by (seed, row, the low 32 bits of `calls`); q: optionally the float32 [n, 8] Q-values it acted on."""
+        ptrs = (C.c_void_p * 6)(*[p.data_ptr() for p in params])
+        self.call("rr_dqn_act", C.byref(ptrs), C.c_void_p(obs.data_ptr()), n, float(min(max(epsilon, 0.0), 1.0)), int(seed),
+                  calls & 0xFFFFFFFF, C.c_void_p(actions.data_ptr()), C.c_void_p(q.data_ptr()) if q is not None else None,
+                  self.stream() if stream is None else stream)

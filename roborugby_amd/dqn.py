@@ -32,6 +32,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
+from .env import STATUS_NOT_READY, STATUS_WAS_RESET
+
 
 class _WideBatchLinear(torch.autograd.Function):
     """y = x W^T + b for a batch far wider than the layer (32,768 samples against 8..256 features).  The forward is F.linear.
@@ -81,13 +84,15 @@ class DeepQNetwork(nn.Module):
         return _linear(self.fc3, x)
 
 
-class BatchedDQNAgent:
-    """DQNAgent (Training_DQN_pytorch.py:70-197) with [N]-batched choose_action/store_transition and device replay."""
+class _ReplayAgent:
+    """What BatchedDQNAgent and PixelDQNAgent share: hyper-parameters, counters, the seeded generator, the replay ring, the rr_dqn handle,
+    the torch paths of acting / storing / learning, the per-transition schedules (module docstring) and the checkpoint.  A subclass
+    builds its network (`make_net`, called after the seeding), names the shape and dtype of an observation, sets `self.optimizer`
+    (attribute or property) and calls _open_handle once it knows whether its kernels apply."""
     PERMUTE_LIMIT = 1 << 20  # sample without replacement (reference: np.random.choice(replace=False)) while a permutation is cheap
 
-    def __init__(self, gamma=.99, epsilon=1.0, lr=.0005, input_dims=11, batch_size=2500, n_actions=8,
-                 max_mem_size=500000, eps_end=0.2, eps_dec=.999997, fc1_dims=256, fc2_dims=256,
-                 target_update_freq=100000, device="cpu", seed=0, use_graph=True, fused=None):
+    def __init__(self, make_net, obs_shape, obs_dtype, gamma, epsilon, batch_size, n_actions, max_mem_size, eps_end, eps_dec,
+                 target_update_freq, device, seed):
         self.gamma, self.epsilon, self.eps_end, self.eps_dec = gamma, epsilon, eps_end, eps_dec
         self.n_actions, self.mem_size, self.batch_size = n_actions, int(max_mem_size), int(batch_size)
         self.target_update_freq = int(target_update_freq)
@@ -95,55 +100,164 @@ class BatchedDQNAgent:
         self.mem_cntr = 0            # transitions stored so far (the reference's mem_cntr)
         self._eps_cntr = 0           # ... of which the epsilon schedule has already been charged
         self._next_target_sync = self.target_update_freq
-        self.target_syncs = 0
-        self.updates = 0
+        self.target_syncs, self.updates, self.last_loss = 0, 0, None
+        self._act_calls = 0  # fused choose_action calls so far: keys the kernel's epsilon draws (checkpointed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
         self._seed = int(seed)
         torch.manual_seed(seed)
-        self.Q_eval = DeepQNetwork(lr, input_dims, fc1_dims, fc2_dims, n_actions).to(self.device)
-        if self.device.type == "cuda":
-            self.Q_eval.optimizer = torch.optim.Adam(self.Q_eval.parameters(), lr=lr, fused=True, capturable=True)
+        self.Q_eval = make_net()
         self.Q_target = copy.deepcopy(self.Q_eval)
         m, d = self.mem_size, self.device
-        self.state_memory = torch.zeros(m, input_dims, dtype=torch.float32, device=d)
-        self.new_state_memory = torch.zeros(m, input_dims, dtype=torch.float32, device=d)
+        self.state_memory = torch.zeros((m,) + tuple(obs_shape), dtype=obs_dtype, device=d)
+        self.new_state_memory = torch.zeros((m,) + tuple(obs_shape), dtype=obs_dtype, device=d)
         self.action_memory = torch.zeros(m, dtype=torch.int64, device=d)
         self.reward_memory = torch.zeros(m, dtype=torch.float32, device=d)
         self.terminal_memory = torch.zeros(m, dtype=torch.bool, device=d)
-        self.last_loss = None
-        self.use_graph = bool(use_graph)
-        # The fused learn step (include/roborugby_amd.h: rr_dqn_update; csrc/rr_dqn.hip): forward of both nets, TD target,
-        # backward, weight-gradient reduction and Adam in two launches on the fp32 matrix cores -- for exactly this network
-        # (11 -> 256 -> 256 -> 8) on the GPU, batch a multiple of 64.  Default: on whenever it applies.  Off: the PyTorch path
-        # (autograd + torch.optim.Adam), which is also the reference the fused step is tested against.
-        can_fuse = (self.device.type == "cuda" and (input_dims, fc1_dims, fc2_dims, n_actions) == (11, 256, 256, 8)
-                    and self.batch_size % 64 == 0)
+        self._dqn = None
+
+    def _open_handle(self, fused, can_fuse, needs):
+        """self.fused (None: on whenever the kernels apply) and, when it is on, the rr_dqn handle (_lib.DqnHandle)"""
         self.fused = can_fuse if fused is None else bool(fused)
         if self.fused and not can_fuse:
-            raise ValueError("fused=True needs a GPU, the reference's 11-256-256-8 network and a batch that is a multiple of 64")
-        self._fused_h = None
-        self._lr, self._betas, self._adam_eps = lr, (0.9, 0.999), 1e-8
+            raise ValueError(f"fused=True needs {needs}")
         if self.fused:
-            from . import _lib
-            self._rrlib = _lib.load()
-            h = C.c_void_p()
-            _lib.check_dqn(self._rrlib.rr_dqn_create(self.device.index or 0, C.byref(h)), "rr_dqn_create", self._rrlib)
-            self._fused_h = h
-            self._fused_loss = torch.zeros(1, device=self.device)
-        self._act_calls = 0  # choose_action calls so far: keys the fused kernel's epsilon draws (checkpointed)
+            self._dqn = _lib.DqnHandle(self.device)
+
+    _fused_h = property(lambda self: self._dqn.h if self._dqn else None)  # the C-ABI's handle and library, as tests and tools drive them
+    _rrlib = property(lambda self: self._dqn.lib)
 
     def close(self):
         """rr_dqn_destroy: the handle holds the per-workgroup partial gradients and the Adam moments (~73 MB of device memory)."""
-        h, self._fused_h = getattr(self, "_fused_h", None), None
-        if h:
-            self._rrlib.rr_dqn_destroy(h)
+        if getattr(self, "_dqn", None):
+            self._dqn.close()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    def _epsilon_greedy(self, greedy, eps):
+        """the torch path of choose_action (Training_DQN_pytorch.py:138-149): int32 [n] from the greedy actions"""
+        if eps <= 0:
+            return greedy.to(torch.int32)
+        n = greedy.shape[0]
+        rand = torch.randint(0, self.n_actions, (n,), generator=self.gen, device=self.device)
+        explore = torch.rand(n, generator=self.gen, device=self.device) <= eps
+        return torch.where(explore, rand, greedy).to(torch.int32)
+
+    @staticmethod
+    def _compact(state, action, reward, state_, done, valid):
+        """the rows with valid=True (None: all), in row order"""
+        action, reward, done = action.reshape(-1), reward.reshape(-1), done.reshape(-1)
+        if valid is not None:
+            idx = valid.reshape(-1).nonzero(as_tuple=True)[0]
+            state, action, reward, state_, done = state[idx], action[idx], reward[idx], state_[idx], done[idx]
+        return state, action, reward, state_, done
+
+    def _ring_write(self, state, action, reward, state_, done):
+        """the torch path of store_transition (Training_DQN_pytorch.py:126-136) for n rows at once"""
+        n = state.shape[0]
+        if n == 0:
+            return
+        pos = (self.mem_cntr + torch.arange(n, device=self.device)) % self.mem_size
+        self.state_memory[pos] = state.to(self.state_memory.dtype)
+        self.new_state_memory[pos] = state_.to(self.state_memory.dtype)
+        self.action_memory[pos] = action.long()
+        self.reward_memory[pos] = reward.float()
+        self.terminal_memory[pos] = done.bool()
+        self.mem_cntr += n
+
+    def _sample(self, max_mem):
+        if max_mem <= self.PERMUTE_LIMIT:
+            return torch.randperm(max_mem, generator=self.gen, device=self.device)[:self.batch_size]  # replace=False
+        # a multi-million-entry memory: independent draws (two of B draws coincide with probability ~B^2 / 2 max_mem per batch)
+        return torch.randint(0, max_mem, (self.batch_size,), generator=self.gen, device=self.device)
+
+    def _learn_core(self, max_mem):
+        """sampling + TD target + one Adam step (Training_DQN_pytorch.py:156-186); everything on the device, no host sync"""
+        self.optimizer.zero_grad(set_to_none=False)
+        batch = self._sample(max_mem)
+        q_eval = self.Q_eval(self.state_memory[batch]).gather(1, self.action_memory[batch].view(-1, 1)).squeeze(1)
+        with torch.no_grad():
+            q_next = self.Q_target(self.new_state_memory[batch]).masked_fill(self.terminal_memory[batch].view(-1, 1), 0.0)
+            q_target = self.reward_memory[batch] + self.gamma * q_next.max(dim=1)[0]
+        loss = F.mse_loss(q_eval, q_target)
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach()
+
+    _learn_step = _learn_core  # what learn() runs: a subclass with kernels or a captured graph chooses here
+
+    def learn(self):
+        """One gradient step (Training_DQN_pytorch.py:151-191) + the per-transition schedules (module docstring)."""
+        if self.mem_cntr < self.batch_size:
+            return None
+        loss = self._learn_step(min(self.mem_size, self.mem_cntr))
+        self.updates += 1
+        # the reference syncs when mem_cntr hits a multiple of target_update_freq; with N transitions per call the
+        # counter jumps, so sync whenever a multiple has been crossed
+        if self.mem_cntr >= self._next_target_sync:
+            with torch.no_grad():  # in place: a captured graph keeps reading these very tensors
+                for pt, pe in zip(self.Q_target.parameters(), self.Q_eval.parameters()):
+                    pt.copy_(pe)
+            self._next_target_sync = (self.mem_cntr // self.target_update_freq + 1) * self.target_update_freq
+            self.target_syncs += 1
+        # one factor eps_dec per transition stored since the schedule was last charged (reference: per learn() = per transition)
+        n_new = self.mem_cntr - self._eps_cntr
+        if n_new > 0:
+            self.epsilon = max(self.epsilon * math.pow(self.eps_dec, n_new), self.eps_end)
+            self._eps_cntr = self.mem_cntr
+        self.last_loss = loss
+        return self.last_loss
+
+    # whole-agent checkpoint like the reference's pickle (Training_DQN_pytorch.py:373-376), without the replay
+    def state_dict(self):
+        return dict(q_eval=self.Q_eval.state_dict(), q_target=self.Q_target.state_dict(), optimizer=self.optimizer.state_dict(),
+                    epsilon=self.epsilon, mem_cntr=self.mem_cntr, updates=self.updates, target_syncs=self.target_syncs,
+                    act_calls=self._act_calls, fused=self.fused)
+
+    def load_state_dict(self, sd):
+        self.Q_eval.load_state_dict(sd["q_eval"])
+        self.Q_target.load_state_dict(sd["q_target"])
+        self.optimizer.load_state_dict(sd["optimizer"])
+        self._act_calls = int(sd.get("act_calls", 0))
+        self.epsilon = sd["epsilon"]
+        self.updates, self.target_syncs = sd.get("updates", 0), sd.get("target_syncs", 0)
+        # The replay memory is not checkpointed (the reference pickles it with the agent), so the transition counter
+        # restarts at what this process has stored: the sync cadence is re-anchored to THAT counter -- a sync within
+        # target_update_freq transitions of the resume, as in an uninterrupted run -- never to the old run's total.
+        self._eps_cntr = self.mem_cntr
+        self._next_target_sync = (self.mem_cntr // self.target_update_freq + 1) * self.target_update_freq
+
+
+class BatchedDQNAgent(_ReplayAgent):
+    """DQNAgent (Training_DQN_pytorch.py:70-197) with [N]-batched choose_action/store_transition and device replay."""
+
+    def __init__(self, gamma=.99, epsilon=1.0, lr=.0005, input_dims=11, batch_size=2500, n_actions=8,
+                 max_mem_size=500000, eps_end=0.2, eps_dec=.999997, fc1_dims=256, fc2_dims=256,
+                 target_update_freq=100000, device="cpu", seed=0, use_graph=True, fused=None):
+        def make_net():
+            net = DeepQNetwork(lr, input_dims, fc1_dims, fc2_dims, n_actions).to(device)
+            if torch.device(device).type == "cuda":
+                net.optimizer = torch.optim.Adam(net.parameters(), lr=lr, fused=True, capturable=True)
+            return net
+        super().__init__(make_net, (input_dims,), torch.float32, gamma, epsilon, batch_size, n_actions, max_mem_size, eps_end, eps_dec,
+                         target_update_freq, device, seed)
+        self.use_graph = bool(use_graph)
+        self._lr, self._betas, self._adam_eps = lr, (0.9, 0.999), 1e-8
+        # The fused learn step (include/roborugby_amd.h: rr_dqn_update; csrc/rr_dqn.hip): forward of both nets, TD target,
+        # backward, weight-gradient reduction and Adam in two launches on the fp32 matrix cores -- for exactly this network
+        # (11 -> 256 -> 256 -> 8) on the GPU, batch a multiple of 64.  Default: on whenever it applies.  Off: the PyTorch path
+        # (autograd + torch.optim.Adam), which is also the reference the fused step is tested against.
+        can_fuse = (self.device.type == "cuda" and (input_dims, fc1_dims, fc2_dims, n_actions) == (11, 256, 256, 8)
+                    and self.batch_size % 64 == 0)
+        self._open_handle(fused, can_fuse, "a GPU, the reference's 11-256-256-8 network and a batch that is a multiple of 64")
+        if self.fused:
+            self._fused_loss = torch.zeros(1, device=self.device)
+
+    optimizer = property(lambda self: self.Q_eval.optimizer)  # (where the reference keeps it)
 
     @torch.no_grad()
     def choose_action(self, observation, epsilon_override=None):
@@ -152,12 +266,7 @@ class BatchedDQNAgent:
         n = observation.shape[0]
         if self.fused and n % 64 == 0 and observation.dtype == torch.float32 and observation.shape[1] == 11:
             return self._act_fused(observation, eps)  # one launch: tiled forward on the matrix cores + argmax + epsilon draw
-        greedy = self.Q_eval(observation).argmax(dim=1)
-        if eps <= 0:
-            return greedy.to(torch.int32)
-        rand = torch.randint(0, self.n_actions, (n,), generator=self.gen, device=self.device)
-        explore = torch.rand(n, generator=self.gen, device=self.device) <= eps
-        return torch.where(explore, rand, greedy).to(torch.int32)
+        return self._epsilon_greedy(self.Q_eval(observation).argmax(dim=1), eps)
 
     @torch.no_grad()
     def store_transition(self, state, action, reward, state_, done, valid=None):
@@ -166,23 +275,10 @@ class BatchedDQNAgent:
         if (self.fused and state.dtype == torch.float32 and state_.dtype == torch.float32 and reward.dtype == torch.float32
                 and state.shape[0] <= self.mem_size):
             return self._store_fused(state, action, reward, state_, done, valid)
-        if valid is not None:
-            idx = valid.nonzero(as_tuple=True)[0]
-            state, action, reward, state_, done = state[idx], action[idx], reward[idx], state_[idx], done[idx]
-        n = state.shape[0]
-        if n == 0:
-            return
-        pos = (self.mem_cntr + torch.arange(n, device=self.device)) % self.mem_size
-        self.state_memory[pos] = state.float()
-        self.new_state_memory[pos] = state_.float()
-        self.action_memory[pos] = action.long()
-        self.reward_memory[pos] = reward.float()
-        self.terminal_memory[pos] = done.bool()
-        self.mem_cntr += n
+        self._ring_write(*self._compact(state, action, reward, state_, done, valid))
 
     def _store_fused(self, state, action, reward, state_, done, valid):
         """rr_dqn_store: the compaction of the valid rows and the five ring writes in one launch"""
-        from . import _lib
         n = state.shape[0]
         s, s2, r = state.contiguous(), state_.contiguous(), reward.contiguous()
         a = action.to(torch.int32).contiguous()
@@ -191,34 +287,22 @@ class BatchedDQNAgent:
         if not hasattr(self, "_store_count"):
             self._store_count = torch.zeros(1, dtype=torch.int32, device=self.device)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        _lib.check_dqn(self._rrlib.rr_dqn_store(self._fused_h, p(s), p(a), p(r), p(s2), p(d), p(v), n, self.mem_cntr, self.mem_size,
-                                            p(self.state_memory), p(self.new_state_memory), p(self.action_memory), p(self.reward_memory),
-                                            p(self.terminal_memory), p(self._store_count),
-                                            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "rr_dqn_store", self._rrlib)
+        self._dqn.call("rr_dqn_store", p(s), p(a), p(r), p(s2), p(d), p(v), n, self.mem_cntr, self.mem_size, p(self.state_memory),
+                       p(self.new_state_memory), p(self.action_memory), p(self.reward_memory), p(self.terminal_memory), p(self._store_count),
+                       self._dqn.stream())
         self.mem_cntr += n if v is None else int(self._store_count.item())  # (the one host read of the call, as in the PyTorch path)
 
-    def _sample(self, max_mem):
-        if max_mem <= self.PERMUTE_LIMIT:
-            return torch.randperm(max_mem, generator=self.gen, device=self.device)[:self.batch_size]  # replace=False
-        # a multi-million-entry memory: independent draws (two of B draws coincide with probability ~B^2 / 2 max_mem per batch)
-        return torch.randint(0, max_mem, (self.batch_size,), generator=self.gen, device=self.device)
-
     def _act_fused(self, observation, eps):
-        from . import _lib
         obs = observation.contiguous()
         n = obs.shape[0]
         out = torch.empty(n, dtype=torch.int32, device=self.device)
-        ptrs = (C.c_void_p * 6)(*[p.data_ptr() for p in self.Q_eval.parameters()])
         self._act_calls += 1
-        _lib.check_dqn(self._rrlib.rr_dqn_act(self._fused_h, C.byref(ptrs), C.c_void_p(obs.data_ptr()), n, float(min(max(eps, 0.0), 1.0)),
-                                          int(self._seed), self._act_calls & 0xFFFFFFFF, C.c_void_p(out.data_ptr()), None,
-                                          C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "rr_dqn_act", self._rrlib)
+        self._dqn.act(self.Q_eval.parameters(), obs, n, eps, self._seed, self._act_calls, out)
         self._keep_obs = obs  # read asynchronously
         return out
 
     def _fused_args(self, batch):
-        from . import _lib
-        a = _lib.RRDqnArgs()
+        a =_lib.RRDqnArgs()
         a.struct_size, a.batch = C.sizeof(_lib.RRDqnArgs), int(batch.shape[0])
         for k, (pe, pt) in enumerate(zip(self.Q_eval.parameters(), self.Q_target.parameters())):
             assert pe.is_contiguous() and pt.is_contiguous() and pe.dtype == torch.float32
@@ -233,22 +317,17 @@ class BatchedDQNAgent:
 
     def _learn_fused(self, max_mem):
         """sampling in PyTorch (one or two kernels), everything else in rr_dqn_update's two launches"""
-        from . import _lib
         batch = self._sample(max_mem).contiguous()
-        args = self._fused_args(batch)
-        _lib.check_dqn(self._rrlib.rr_dqn_update(self._fused_h, C.byref(args), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                   "rr_dqn_update", self._rrlib)
+        self._dqn.call("rr_dqn_update", C.byref(self._fused_args(batch)), self._dqn.stream())
         self._keep = batch  # the launch reads it asynchronously
         return self._fused_loss[0]
 
     def fused_grads(self, batch):
         """gradient of the loss on the given replay rows as rr_dqn_grads computes it, as a dict keyed like Q_eval's parameters"""
-        from . import _lib
         n = self._rrlib.rr_dqn_param_count()
         flat = torch.empty(n, device=self.device)
         args = self._fused_args(batch.contiguous())
-        _lib.check_dqn(self._rrlib.rr_dqn_grads(self._fused_h, C.byref(args), C.c_void_p(flat.data_ptr()),
-                                            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "rr_dqn_grads", self._rrlib)
+        self._dqn.call("rr_dqn_grads", C.byref(args), C.c_void_p(flat.data_ptr()), self._dqn.stream())
         torch.cuda.current_stream(self.device).synchronize()
         names = ["fc2.weight", "fc1.weight", "fc3.weight", "fc1.bias", "fc2.bias", "fc3.bias"]  # the handle's flat order
         shapes = dict(self.Q_eval.named_parameters())
@@ -258,25 +337,6 @@ class BatchedDQNAgent:
             out[nm] = flat[off:off + k].view_as(shapes[nm]).clone()
             off += k
         return out, float(self._fused_loss[0])
-
-    def _learn_core(self, max_mem):
-        """sampling + TD target + one Adam step (Training_DQN_pytorch.py:156-186); everything on the device, no host sync"""
-        self.Q_eval.optimizer.zero_grad(set_to_none=False)
-        batch = self._sample(max_mem)
-        state_batch = self.state_memory[batch]
-        new_state_batch = self.new_state_memory[batch]
-        reward_batch = self.reward_memory[batch]
-        terminal_batch = self.terminal_memory[batch]
-        action_batch = self.action_memory[batch]
-        q_eval = self.Q_eval(state_batch).gather(1, action_batch.view(-1, 1)).squeeze(1)
-        with torch.no_grad():
-            q_next = self.Q_target(new_state_batch)
-            q_next = q_next.masked_fill(terminal_batch.view(-1, 1), 0.0)
-            q_target = reward_batch + self.gamma * q_next.max(dim=1)[0]
-        loss = self.Q_eval.loss(q_target, q_eval)
-        loss.backward()
-        self.Q_eval.optimizer.step()
-        return loss.detach()
 
     def _try_capture(self, max_mem):
         """Once the replay memory is full the learn step has a fixed shape: capture it into a HIP graph (the step is ~25
@@ -316,43 +376,18 @@ class BatchedDQNAgent:
             self.gen.set_state(saved_gen)
             print(f"[dqn] learn() stays eager (graph capture failed: {type(ex).__name__}: {ex})", flush=True)
 
-    def learn(self):
-        """One gradient step (Training_DQN_pytorch.py:151-191) + the per-transition schedules (module docstring)."""
-        if self.mem_cntr < self.batch_size:
-            return None
-        max_mem = min(self.mem_size, self.mem_cntr)
+    def _learn_step(self, max_mem):
         if self.fused:
-            loss = self._learn_fused(max_mem)
-        elif self.use_graph and self.device.type == "cuda" and max_mem == self.mem_size and not getattr(self, "_graph_tried", False):
+            return self._learn_fused(max_mem)
+        if self.use_graph and self.device.type == "cuda" and max_mem == self.mem_size and not getattr(self, "_graph_tried", False):
             self._try_capture(max_mem)
-        if self.fused:
-            pass
-        elif getattr(self, "_graph", None) is not None and self._graph_mem == max_mem:
+        if getattr(self, "_graph", None) is not None and self._graph_mem == max_mem:
             self._graph.replay()
-            loss = self._graph_loss
-        else:
-            loss = self._learn_core(max_mem)
-        self.updates += 1
-        # the reference syncs when mem_cntr hits a multiple of target_update_freq; with N transitions per call the
-        # counter jumps, so sync whenever a multiple has been crossed
-        if self.mem_cntr >= self._next_target_sync:
-            with torch.no_grad():  # in place: a captured graph keeps reading these very tensors
-                for pt, pe in zip(self.Q_target.parameters(), self.Q_eval.parameters()):
-                    pt.copy_(pe)
-            self._next_target_sync = (self.mem_cntr // self.target_update_freq + 1) * self.target_update_freq
-            self.target_syncs += 1
-        # one factor eps_dec per transition stored since the schedule was last charged (reference: per learn() = per transition)
-        n_new = self.mem_cntr - self._eps_cntr
-        if n_new > 0:
-            self.epsilon = max(self.epsilon * math.pow(self.eps_dec, n_new), self.eps_end)
-            self._eps_cntr = self.mem_cntr
-        self.last_loss = loss
-        return self.last_loss
+            return self._graph_loss
+        return self._learn_core(max_mem)
 
-    # whole-agent checkpoint like the reference's pickle (Training_DQN_pytorch.py:373-376), without the replay
     def _fused_adam(self, state=None):
         """the fused step's Adam moments + step count out of (state=None) or into the handle"""
-        from . import _lib
         n = self._rrlib.rr_dqn_param_count()
         if state is None:
             m1, m2 = torch.empty(n, device=self.device), torch.empty(n, device=self.device)
@@ -360,9 +395,8 @@ class BatchedDQNAgent:
         else:
             m1, m2 = state["exp_avg"].to(self.device).contiguous(), state["exp_avg_sq"].to(self.device).contiguous()
             step = C.c_int64(int(state["step"]))
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check_dqn(self._rrlib.rr_dqn_adam_state(self._fused_h, C.c_void_p(m1.data_ptr()), C.c_void_p(m2.data_ptr()), C.byref(step),
-                                                 0 if state is None else 1, st), "rr_dqn_adam_state", self._rrlib)
+        self._dqn.call("rr_dqn_adam_state", C.c_void_p(m1.data_ptr()), C.c_void_p(m2.data_ptr()), C.byref(step), 0 if state is None else 1,
+                       self._dqn.stream())
         torch.cuda.current_stream(self.device).synchronize()
         return dict(exp_avg=m1, exp_avg_sq=m2, step=step.value)
 
@@ -396,10 +430,8 @@ class BatchedDQNAgent:
     def state_dict(self):
         """Both optimizer representations travel, so a checkpoint written by the fused agent resumes under --no-fused and the
         other way round: `optimizer` (torch.optim.Adam's) and `fused_adam` (flat moments + step) describe the same Adam state."""
-        opt = self.Q_eval.optimizer.state_dict()
-        sd = dict(q_eval=self.Q_eval.state_dict(), q_target=self.Q_target.state_dict(), epsilon=self.epsilon, mem_cntr=self.mem_cntr,
-                  next_target_sync=self._next_target_sync, updates=self.updates, target_syncs=self.target_syncs,
-                  act_calls=self._act_calls, fused=self.fused)
+        sd = dict(super().state_dict(), next_target_sync=self._next_target_sync)
+        opt = sd["optimizer"]
         if self.fused:
             sd["fused_adam"] = self._fused_adam()
             if sd["fused_adam"]["step"] > 0:  # the torch optimizer is never stepped in fused mode: write the moments in its format too
@@ -412,9 +444,7 @@ class BatchedDQNAgent:
         return sd
 
     def load_state_dict(self, sd, lr_override=0.0, epsilon_override=0.0, eps_dec_override=0.0):
-        self.Q_eval.load_state_dict(sd["q_eval"])
-        self.Q_target.load_state_dict(sd["q_target"])
-        self.Q_eval.optimizer.load_state_dict(sd["optimizer"])
+        super().load_state_dict(sd)
         if self.fused:
             flat = sd.get("fused_adam") or self._flat_from_torch_adam(sd["optimizer"])
             if flat is not None:
@@ -422,14 +452,6 @@ class BatchedDQNAgent:
             elif sd.get("updates", 0) > 0:
                 import warnings
                 warnings.warn("checkpoint carries no Adam moments for the fused learn step: Adam restarts from zero moments")
-        self._act_calls = int(sd.get("act_calls", 0))
-        self.epsilon = sd["epsilon"]
-        self.updates, self.target_syncs = sd.get("updates", 0), sd.get("target_syncs", 0)
-        # The replay memory is not checkpointed (the reference pickles it with the agent), so the transition counter
-        # restarts at what this process has stored: the sync cadence is re-anchored to THAT counter -- a sync within
-        # target_update_freq transitions of the resume, as in an uninterrupted run -- never to the old run's total.
-        self._eps_cntr = self.mem_cntr
-        self._next_target_sync = (self.mem_cntr // self.target_update_freq + 1) * self.target_update_freq
         if lr_override > 0:  # Training_DQN_pytorch.py:297-303
             self._lr = lr_override
             for g in self.Q_eval.optimizer.param_groups:
@@ -459,58 +481,23 @@ class PixelQNetwork(nn.Module):
         return self.fc2(x)
 
 
-class PixelDQNAgent:
+class PixelDQNAgent(_ReplayAgent):
     """BatchedDQNAgent's surface on the pixels of PixelObservation(size=64, stack=channels / 3).  Acting -- every row, every step -- is
     rr_cnn_act (one HIP kernel on the bf16 matrix cores, csrc/rr_cnn.hip) where it applies: on the GPU, contiguous uint8 rows, channels
     in {3, 6, 9, 12}, 8 actions; anything else, and fused=False, goes through the torch module.  Learning is PyTorch autograd on the same
-    parameters (MSE on r + gamma max Q_target, Adam, target sync and the epsilon schedule as in BatchedDQNAgent), the replay ring holds
+    parameters (MSE on r + gamma max Q_target, Adam, target sync and the epsilon schedule: _ReplayAgent's), the replay ring holds
     uint8 frames and is written with torch indexing: 2 * channels * 4096 + 13 bytes per transition."""
     FUSED_CHANNELS = (3, 6, 9, 12)
+    PERMUTE_LIMIT = math.inf  # always a permutation: a ring of frames never grows to where one costs
 
     def __init__(self, channels=12, gamma=.99, epsilon=1.0, lr=.0005, batch_size=256, n_actions=8, max_mem_size=65536, eps_end=0.2,
                  eps_dec=.999997, target_update_freq=100000, device="cpu", seed=0, fused=None):
-        self.channels, self.gamma, self.epsilon, self.eps_end, self.eps_dec = int(channels), gamma, epsilon, eps_end, eps_dec
-        self.n_actions, self.mem_size, self.batch_size = n_actions, int(max_mem_size), int(batch_size)
-        self.target_update_freq = int(target_update_freq)
-        self.device = torch.device(device)
-        self.mem_cntr, self._eps_cntr, self._next_target_sync = 0, 0, self.target_update_freq
-        self.target_syncs, self.updates, self.last_loss = 0, 0, None
-        self.gen = torch.Generator(device=self.device)
-        self.gen.manual_seed(seed)
-        self._seed = int(seed)
-        torch.manual_seed(seed)
-        self.Q_eval = PixelQNetwork(self.channels, n_actions).to(self.device)
-        self.Q_target = copy.deepcopy(self.Q_eval)
+        self.channels = int(channels)
+        super().__init__(lambda: PixelQNetwork(self.channels, n_actions).to(device), (self.channels, 64, 64), torch.uint8, gamma, epsilon,
+                         batch_size, n_actions, max_mem_size, eps_end, eps_dec, target_update_freq, device, seed)
         self.optimizer = torch.optim.Adam(self.Q_eval.parameters(), lr=lr)
-        m, d, shape = self.mem_size, self.device, (self.channels, 64, 64)
-        self.state_memory = torch.zeros((m,) + shape, dtype=torch.uint8, device=d)
-        self.new_state_memory = torch.zeros((m,) + shape, dtype=torch.uint8, device=d)
-        self.action_memory = torch.zeros(m, dtype=torch.int64, device=d)
-        self.reward_memory = torch.zeros(m, dtype=torch.float32, device=d)
-        self.terminal_memory = torch.zeros(m, dtype=torch.bool, device=d)
         can_fuse = self.device.type == "cuda" and self.channels in self.FUSED_CHANNELS and n_actions == 8
-        self.fused = can_fuse if fused is None else bool(fused)
-        if self.fused and not can_fuse:
-            raise ValueError("fused=True needs a GPU, 3 / 6 / 9 / 12 channels and 8 actions")
-        self._fused_h = None
-        if self.fused:
-            from . import _lib
-            self._rrlib = _lib.load()
-            h = C.c_void_p()
-            _lib.check_dqn(self._rrlib.rr_dqn_create(self.device.index or 0, C.byref(h)), "rr_dqn_create", self._rrlib)
-            self._fused_h = h
-        self._act_calls = 0  # choose_action calls so far: keys the kernel's epsilon draws (checkpointed)
-
-    def close(self):
-        h, self._fused_h = getattr(self, "_fused_h", None), None
-        if h:
-            self._rrlib.rr_dqn_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open_handle(fused, can_fuse, "a GPU, 3 / 6 / 9 / 12 channels and 8 actions")
 
     def _rows(self, pixels):
         if pixels.dim() == 5:  # PixelObservation with several robots: [N, R, C, 64, 64], a row per (arena, robot)
@@ -532,15 +519,9 @@ class PixelDQNAgent:
         q = self.Q_eval(pixels)
         if qvalues is not None:
             qvalues.copy_(q)
-        greedy = q.argmax(dim=1)
-        if eps <= 0:
-            return greedy.to(torch.int32)
-        rand = torch.randint(0, self.n_actions, (n,), generator=self.gen, device=self.device)
-        explore = torch.rand(n, generator=self.gen, device=self.device) <= eps
-        return torch.where(explore, rand, greedy).to(torch.int32)
+        return self._epsilon_greedy(q.argmax(dim=1), eps)
 
     def _act_fused(self, pixels, eps, qvalues=None):
-        from . import _lib
         n = pixels.shape[0]
         out = torch.empty(n, dtype=torch.int32, device=self.device)
         params = list(self.Q_eval.parameters())
@@ -549,77 +530,27 @@ class PixelDQNAgent:
             assert qvalues.dtype == torch.float32 and qvalues.is_contiguous() and tuple(qvalues.shape) == (n, 8)
         ptrs = (C.c_void_p * 8)(*[p.data_ptr() for p in params])
         self._act_calls += 1
-        _lib.check_dqn(self._rrlib.rr_cnn_act(self._fused_h, C.byref(ptrs), C.c_void_p(pixels.data_ptr()), n, self.channels,
-                                              float(min(max(eps, 0.0), 1.0)), int(self._seed), self._act_calls & 0xFFFFFFFF,
-                                              C.c_void_p(out.data_ptr()), C.c_void_p(qvalues.data_ptr()) if qvalues is not None else None,
-                                              C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "rr_cnn_act", self._rrlib)
+        self._dqn.call("rr_cnn_act", C.byref(ptrs), C.c_void_p(pixels.data_ptr()), n, self.channels, float(min(max(eps, 0.0), 1.0)),
+                       int(self._seed), self._act_calls & 0xFFFFFFFF, C.c_void_p(out.data_ptr()),
+                       C.c_void_p(qvalues.data_ptr()) if qvalues is not None else None, self._dqn.stream())
         return out
 
     @torch.no_grad()
     def store_transition(self, state, action, reward, state_, done, valid=None):
         """Appends the rows with valid=True (None: all) to the ring, in row order"""
-        state, state_ = self._rows(state), self._rows(state_)
-        if valid is not None:
-            idx = valid.reshape(-1).nonzero(as_tuple=True)[0]
-            state, action, reward, state_, done = state[idx], action.reshape(-1)[idx], reward.reshape(-1)[idx], state_[idx], done.reshape(-1)[idx]
-        n = state.shape[0]
-        if n == 0:
-            return
-        if n > self.mem_size:
-            raise ValueError(f"{n} transitions in one call do not fit a replay ring of {self.mem_size}")
-        pos = (self.mem_cntr + torch.arange(n, device=self.device)) % self.mem_size
-        self.state_memory[pos] = state.to(torch.uint8)
-        self.new_state_memory[pos] = state_.to(torch.uint8)
-        self.action_memory[pos] = action.reshape(-1).long()
-        self.reward_memory[pos] = reward.reshape(-1).float()
-        self.terminal_memory[pos] = done.reshape(-1).bool()
-        self.mem_cntr += n
-
-    def learn(self):
-        """One gradient step on batch_size sampled transitions + the per-transition schedules (BatchedDQNAgent.learn)"""
-        if self.mem_cntr < self.batch_size:
-            return None
-        max_mem = min(self.mem_size, self.mem_cntr)
-        batch = torch.randperm(max_mem, generator=self.gen, device=self.device)[:self.batch_size]
-        self.optimizer.zero_grad(set_to_none=False)
-        q_eval = self.Q_eval(self.state_memory[batch]).gather(1, self.action_memory[batch].view(-1, 1)).squeeze(1)
-        with torch.no_grad():
-            q_next = self.Q_target(self.new_state_memory[batch]).masked_fill(self.terminal_memory[batch].view(-1, 1), 0.0)
-            q_target = self.reward_memory[batch] + self.gamma * q_next.max(dim=1)[0]
-        loss = F.mse_loss(q_eval, q_target)
-        loss.backward()
-        self.optimizer.step()
-        self.updates += 1
-        if self.mem_cntr >= self._next_target_sync:
-            with torch.no_grad():
-                for pt, pe in zip(self.Q_target.parameters(), self.Q_eval.parameters()):
-                    pt.copy_(pe)
-            self._next_target_sync = (self.mem_cntr // self.target_update_freq + 1) * self.target_update_freq
-            self.target_syncs += 1
-        n_new = self.mem_cntr - self._eps_cntr
-        if n_new > 0:
-            self.epsilon = max(self.epsilon * math.pow(self.eps_dec, n_new), self.eps_end)
-            self._eps_cntr = self.mem_cntr
-        self.last_loss = loss.detach()
-        return self.last_loss
+        rows = self._compact(self._rows(state), action, reward, self._rows(state_), done, valid)
+        if rows[0].shape[0] > self.mem_size:
+            raise ValueError(f"{rows[0].shape[0]} transitions in one call do not fit a replay ring of {self.mem_size}")
+        self._ring_write(*rows)
 
     def state_dict(self):
         """the agent without its replay (as BatchedDQNAgent's)"""
-        return dict(kind="pixel", channels=self.channels, q_eval=self.Q_eval.state_dict(), q_target=self.Q_target.state_dict(),
-                    optimizer=self.optimizer.state_dict(), epsilon=self.epsilon, mem_cntr=self.mem_cntr, updates=self.updates,
-                    target_syncs=self.target_syncs, act_calls=self._act_calls, fused=self.fused)
+        return dict(super().state_dict(), kind="pixel", channels=self.channels)
 
     def load_state_dict(self, sd):
         if sd.get("kind") != "pixel" or int(sd["channels"]) != self.channels:
             raise ValueError(f"not a checkpoint of a pixel agent with {self.channels} channels")
-        self.Q_eval.load_state_dict(sd["q_eval"])
-        self.Q_target.load_state_dict(sd["q_target"])
-        self.optimizer.load_state_dict(sd["optimizer"])
-        self._act_calls = int(sd.get("act_calls", 0))
-        self.epsilon = sd["epsilon"]
-        self.updates, self.target_syncs = sd.get("updates", 0), sd.get("target_syncs", 0)
-        self._eps_cntr = self.mem_cntr  # (the replay is not checkpointed: the schedules are re-anchored as in BatchedDQNAgent)
-        self._next_target_sync = (self.mem_cntr // self.target_update_freq + 1) * self.target_update_freq
+        super().load_state_dict(sd)
 
 
 @torch.no_grad()
@@ -634,6 +565,39 @@ def evaluate(env, policy, episodes=1):
         obs, reward, done, info = env.step(policy(obs).view(-1, 1))
         total += reward.double()
     return float(total.mean() / episodes), float(total.std() / episodes)
+
+
+def _log_progress(step, agent, env):
+    """the progress line of train() / train_pixels()"""
+    torch.cuda.synchronize()
+    lr_, _, _, cnt = env.episode_stats()
+    fin = cnt > 0
+    avg = float(lr_[fin].mean()) if bool(fin.any()) else float("nan")
+    print(f"step {step} epsilon {agent.epsilon:.6f} updates {agent.updates} target-syncs {agent.target_syncs} finished-episodes "
+          f"{int(cnt.sum())} avg-last-return {avg:.1f} loss {float(agent.last_loss) if agent.last_loss is not None else float('nan'):.4f}", flush=True)
+
+
+def _save_checkpoint(path, agent, **rest):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(dict(agent=agent.state_dict(), **rest), path)
+
+
+def _write_result(path, res):
+    os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+def _train_result(agent, env, env_steps, seconds, steps, transitions, step_budget_clocks, updates_per_step, rows_per_step, overlap,
+                  eps_dec, eps_end, fused_learn_step, mean_step_reward, preset, dtype, curve):
+    """what train() and train_pixels() both report; updates_per_step: 0 where nothing was learnt"""
+    return dict(env_steps_per_sec=env_steps / seconds, seconds=seconds, num_envs=env.num_envs, steps=steps, transitions=transitions,
+                step_budget_clocks=step_budget_clocks, learn_calls=agent.updates, updates_per_step=updates_per_step,
+                batch_size=agent.batch_size, samples_per_transition=updates_per_step * agent.batch_size / rows_per_step if updates_per_step else 0.0,
+                overlap_learn=overlap, replay_transitions=agent.mem_size, target_update_freq=agent.target_update_freq,
+                target_syncs=agent.target_syncs, epsilon=agent.epsilon, eps_dec=eps_dec, eps_end=eps_end,
+                finished_episodes=int(env.episode_stats()[3].sum()), fused_learn_step=fused_learn_step, mean_step_reward=mean_step_reward,
+                preset=preset, dtype=dtype, curve=curve)
 
 
 def train(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkpoint=None, resume=None,
@@ -711,9 +675,9 @@ def train(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkp
             # the action it accepted): the last call before it runs synchronously -- parked arenas finish, nobody parks
             env.set_step_budget(0)
         observation_, reward, done, info = env.step(acts)
-        real = (info.status & (1024 | 16384)) == 0  # a call that only re-placed the arena, or left its step unfinished, is not a transition
+        real = (info.status & (STATUS_WAS_RESET | STATUS_NOT_READY)) == 0  # a call that only re-placed the arena, or left its step unfinished, is not a transition
         if step_budget_clocks:
-            parked, accepted = (info.status & 16384) != 0, action
+            parked, accepted = (info.status & STATUS_NOT_READY) != 0, action
             if grumpy:
                 accepted_g = action_grumpy
         score_sum += reward
@@ -730,13 +694,7 @@ def train(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkp
         observation = observation_
         obs_grumpy = info.adblGrumpyState
         if log_every and (i + 1) % log_every == 0:
-            torch.cuda.synchronize()
-            lr_, _, ll, cnt = env.episode_stats()
-            fin = cnt > 0
-            avg = float(lr_[fin].mean()) if bool(fin.any()) else float("nan")
-            print(f"step {i + 1} epsilon {agent.epsilon:.6f} updates {agent.updates} target-syncs {agent.target_syncs} finished-episodes "
-                  f"{int(cnt.sum())} avg-last-return {avg:.1f} loss {float(agent.last_loss) if agent.last_loss is not None else float('nan'):.4f}",
-                  flush=True)
+            _log_progress(i + 1, agent, env)
         if eval_every and (i + 1) % eval_every == 0:
             torch.cuda.synchronize()
             te = time.perf_counter()
@@ -749,20 +707,13 @@ def train(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkp
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0 - t_eval
     if checkpoint:
-        os.makedirs(os.path.dirname(os.path.abspath(checkpoint)), exist_ok=True)
-        torch.save(dict(agent=agent.state_dict(), **env.checkpoint_state()), checkpoint)
-    lr_, _, ll, cnt = env.episode_stats()
+        _save_checkpoint(checkpoint, agent, **env.checkpoint_state())
     n_real = int(real_rows.item())
     # env steps = the rows that stepped an arena (auto-reset calls count, as in bench.py's random line they are subtracted only there;
     # NOT_READY rows of the budgeted step never count)
     env_steps = num_envs * steps if not step_budget_clocks else n_real
-    res = dict(env_steps_per_sec=env_steps / dt, seconds=dt, num_envs=num_envs, steps=steps, transitions=n_real,
-               step_budget_clocks=step_budget_clocks,
-               learn_calls=agent.updates, updates_per_step=updates_per_step if learn else 0, batch_size=B,
-               samples_per_transition=(updates_per_step * B / (num_envs * n_teams)) if learn else 0.0, overlap_learn=overlap,
-               replay_transitions=agent.mem_size, target_update_freq=agent.target_update_freq, target_syncs=agent.target_syncs,
-               epsilon=agent.epsilon, eps_dec=eps_dec, eps_end=eps_end, finished_episodes=int(cnt.sum()), fused_learn_step=bool(agent.fused),
-               mean_step_reward=float(score_sum.mean() / steps), preset=preset, dtype=dtype, curve=curve)
+    res = _train_result(agent, env, env_steps, dt, steps, n_real, step_budget_clocks, updates_per_step if learn else 0, num_envs * n_teams,
+                        overlap, eps_dec, eps_end, bool(agent.fused), float(score_sum.mean() / steps), preset, dtype, curve)
     if eval_every:
         # throughput of the rollout alone under the policy training converged to (greedy, contact-seeking), next to the random policy's
         for name, pol in (("greedy", lambda o: agent.choose_action(o, epsilon_override=0.0)),
@@ -777,9 +728,7 @@ def train(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkp
         eval_env.close()
     env.close()
     if out:
-        os.makedirs(os.path.dirname(os.path.abspath(out)) or ".", exist_ok=True)
-        with open(out, "w") as f:
-            json.dump(res, f, indent=1)
+        _write_result(out, res)
     return res
 
 
@@ -798,7 +747,6 @@ def play_hive(checkpoint, num_envs=4096, steps=300, device="cuda:0", seed=0, eps
     record_view: "field" -- the whole arena --, or "ego": what the first hive robot of each recorded arena sees (render_ego: the robot
     in the centre, its front up, 400 arena units across, `record_size` x `record_size` pixels)."""
     import roborugby_amd as rr
-    from .env import STATUS_NOT_READY, STATUS_WAS_RESET
     from .players import Hive, og_twitchy
     env = rr.BatchedRoboRugbyEnv(num_envs, preset=preset, device=device, seed=seed, action_mode="thrust",
                                  step_budget_clocks=step_budget_clocks)
@@ -883,7 +831,6 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
     reports NOT_READY, the hive holds its rows (players.Hive) and the transition is stored by the call that completes the step, with the
     observation and the action the arena accepted.  env-steps are then the rows that stepped an arena, as in train()."""
     import roborugby_amd as rr
-    from .env import STATUS_NOT_READY, STATUS_WAS_RESET
     from .players import Hive, og_twitchy
     if opponents not in ("og_twitchy", None):
         raise ValueError("opponents: 'og_twitchy' or None")
@@ -938,8 +885,7 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
     torch.cuda.synchronize(env.device)
     secs = t0.elapsed_time(t1) / 1e3
     if checkpoint:
-        os.makedirs(os.path.dirname(os.path.abspath(checkpoint)), exist_ok=True)
-        torch.save(dict(agent=agent.state_dict(), mode="train_hive", preset=preset, hive_robots=list(members)), checkpoint)
+        _save_checkpoint(checkpoint, agent, mode="train_hive", preset=preset, hive_robots=list(members))
     n_valid = int(valid_rows.item())
     res = dict(mode="train_hive", preset=preset, dtype=dtype, num_envs=num_envs, steps=steps, hive_robots=list(members), opponents=opponents,
                env_steps_per_sec=(int(real_rows) if step_budget_clocks else num_envs * steps) / secs, seconds=secs,
@@ -954,9 +900,7 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
     agent.close()
     env.close()
     if out:
-        os.makedirs(os.path.dirname(os.path.abspath(out)) or ".", exist_ok=True)
-        with open(out, "w") as f:
-            json.dump(res, f, indent=1)
+        _write_result(out, res)
     return res
 
 
@@ -999,7 +943,7 @@ def train_pixels(num_envs=4096, steps=300, stack=4, span=400.0, mem_size=65536, 
         action = agent.choose_action(pixels)
         before.copy_(pixels)
         pixels, reward, done, info = view.step(action.view(-1, 1))
-        real = (info.status & (1024 | 16384)) == 0  # a call that only re-placed the arena is not a transition
+        real = (info.status & (STATUS_WAS_RESET | STATUS_NOT_READY)) == 0  # a call that only re-placed the arena is not a transition
         score_sum += reward
         real_rows += real.sum()
         if learn:
@@ -1007,34 +951,19 @@ def train_pixels(num_envs=4096, steps=300, stack=4, span=400.0, mem_size=65536, 
             for _ in range(updates_per_step):
                 agent.learn()
         if log_every and (i + 1) % log_every == 0:
-            torch.cuda.synchronize()
-            lr_, _, ll, cnt = env.episode_stats()
-            fin = cnt > 0
-            avg = float(lr_[fin].mean()) if bool(fin.any()) else float("nan")
-            print(f"step {i + 1} epsilon {agent.epsilon:.6f} updates {agent.updates} target-syncs {agent.target_syncs} finished-episodes "
-                  f"{int(cnt.sum())} avg-last-return {avg:.1f} loss {float(agent.last_loss) if agent.last_loss is not None else float('nan'):.4f}",
-                  flush=True)
+            _log_progress(i + 1, agent, env)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if checkpoint:
-        os.makedirs(os.path.dirname(os.path.abspath(checkpoint)), exist_ok=True)
-        torch.save(dict(agent=agent.state_dict(), **env.checkpoint_state()), checkpoint)
-    lr_, _, ll, cnt = env.episode_stats()
-    n_real = int(real_rows.item())
-    res = dict(env_steps_per_sec=num_envs * steps / dt, seconds=dt, num_envs=num_envs, steps=steps, transitions=n_real,
-               step_budget_clocks=0, learn_calls=agent.updates, updates_per_step=updates_per_step if learn else 0, batch_size=B,
-               samples_per_transition=(updates_per_step * B / num_envs) if learn else 0.0, overlap_learn=False,
-               replay_transitions=agent.mem_size, target_update_freq=agent.target_update_freq, target_syncs=agent.target_syncs,
-               epsilon=agent.epsilon, eps_dec=eps_dec, eps_end=eps_end, finished_episodes=int(cnt.sum()), fused_learn_step=False,
-               mean_step_reward=float(score_sum.mean() / max(steps, 1)), preset="T", dtype=dtype, curve=[],
-               stack=int(stack), span=float(span), fused_act=bool(agent.fused),
+        _save_checkpoint(checkpoint, agent, **env.checkpoint_state())
+    res = _train_result(agent, env, num_envs * steps, dt, steps, int(real_rows.item()), 0, updates_per_step if learn else 0, num_envs, False,
+                        eps_dec, eps_end, False, float(score_sum.mean() / max(steps, 1)), "T", dtype, [])
+    res.update(stack=int(stack), span=float(span), fused_act=bool(agent.fused),
                loss=float(agent.last_loss) if agent.last_loss is not None else None)
     agent.close()
     env.close()
     if out:
-        os.makedirs(os.path.dirname(os.path.abspath(out)) or ".", exist_ok=True)
-        with open(out, "w") as f:
-            json.dump(res, f, indent=1)
+        _write_result(out, res)
     return res
 
 

@@ -75,13 +75,10 @@ class Hive:
                                                               for p in params):
             raise ValueError("agent: the reference's 11-256-256-8 network (six contiguous float32 tensors on the env's device)")
         self._params = params  # (kept alive; the pointers are read at every act(): in-place updates of a learning agent are seen)
-        self._rrlib = _lib.load()
-        self._own_h = None
-        self._dqn_h = getattr(agent, "_fused_h", None)
-        if not self._dqn_h:
-            h = C.c_void_p()
-            _lib.check_dqn(self._rrlib.rr_dqn_create(env.device.index or 0, C.byref(h)), "rr_dqn_create", self._rrlib)
-            self._dqn_h = self._own_h = h
+        self._dqn = getattr(agent, "_dqn", None)  # the rr_dqn handle (_lib.DqnHandle): a fused agent's is borrowed, never closed here
+        self._owns = not (self._dqn and self._dqn.h)
+        if self._owns:
+            self._dqn = _lib.DqnHandle(env.device)
         self._agent = agent  # (kept alive: a borrowed rr_dqn handle is the agent's)
         self.rows = (N * nr + 63) // 64 * 64
         dev = env.device
@@ -96,15 +93,19 @@ class Hive:
         self.calls = 0
 
     def close(self):
-        h, self._own_h = self._own_h, None
-        if h:
-            self._rrlib.rr_dqn_destroy(h)
+        if getattr(self, "_owns", False):
+            self._dqn.close()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    @property
+    def _dqn_h(self):
+        """the rr_dqn handle act() runs on (None: its owner has closed it)"""
+        return self._dqn.h
 
     @property
     def assign(self):
@@ -127,12 +128,8 @@ class Hive:
         return self._held.view(torch.bool)
 
     def _dqn_act(self, actions, stream):
-        from . import _lib
         self.calls += 1
-        ptrs = (C.c_void_p * 6)(*[p.data_ptr() for p in self._params])
-        _lib.check_dqn(self._rrlib.rr_dqn_act(self._dqn_h, C.byref(ptrs), C.c_void_p(self._obs.data_ptr()), self.rows,
-                                              min(max(self.epsilon, 0.0), 1.0), self.seed, self.calls & 0xFFFFFFFF,
-                                              C.c_void_p(actions.data_ptr()), None, stream), "rr_dqn_act", self._rrlib)
+        self._dqn.act(self._params, self._obs, self.rows, self.epsilon, self.seed, self.calls, actions, stream=stream)
 
     def _act_held(self, out, stream):
         """act() under the budgeted step: observe (held rows kept) -> the agent's fresh answers -> commit, on the current stream"""
@@ -156,7 +153,7 @@ class Hive:
         if out is None:
             out = torch.zeros(N, 2 * nr, dtype=torch.float32, device=env.device)
         assert out.dtype == torch.float32 and out.shape == (N, 2 * nr) and out.is_contiguous()
-        stream = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+        stream = self._dqn.stream()
         if status is None and env.has_had_budget:
             return self._act_held(out, stream)
         _lib.check(env._lib.rr_hive_observe(env._h, self.mask, self.kind, C.c_void_p(self._assign.data_ptr()),

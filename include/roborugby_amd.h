@@ -463,6 +463,49 @@ int rr_dqn_adam_state(rr_dqn *dqn, float *exp_avg, float *exp_avg_sq, int64_t *s
 int rr_cnn_act(rr_dqn *dqn, const float *const params[8], const uint8_t *pixels, int32_t n, int32_t channels, float epsilon,
                uint64_t seed, uint32_t call, int32_t *actions, float *qvalues, void *stream);
 
+/* ---- the frame-sharing pixel replay (roborugby_amd/csrc/rr_frames.hpp, rr_frames.hip; roborugby_amd/frame_replay.py FrameReplay): a ring
+ * that stores every frame ONCE instead of two whole stacked observations per transition.  The caller owns the ring (device memory):
+ *   frames  u8  [slots, rows, frame_bytes]   the newest frame of every row after push k, in slot k % slots
+ *   age     u8  [slots, rows]                frames since the row's stack restarted: 0 where the row is `first` in this push (push 0:
+ *                                            every row), otherwise min(age of push k - 1, plus 1, 255)
+ *   action  i32 [slots, rows], reward f32 [slots, rows]
+ *   flags   u8  [slots, rows]                bit 0: the step from push k - 1 to push k is a real transition of this row; bit 1: it ended
+ *                                            the episode (terminal).  Push 0 writes 0.
+ * `head` = the number of pushes so far, kept by the caller; push number k = head lands in slot head % slots.
+ * The observation of row i at push k with stack S, oldest frame first: frame j (0 .. S-1) is the one of push k - min(S-1-j, age[k][i])
+ * (PixelObservation's rule: a restarted row has every slot equal to its first frame).  Transition (k, i) = the stack at k - 1, action[k],
+ * reward[k], terminal bit [k], the stack at k.  Sampleable: lo <= k <= head - 1 with lo = max(1, head - slots + S): every frame such a
+ * transition needs is still in the ring.
+ * Both entries take the rr_dqn handle for its device and the error string; they keep nothing in it.  Both return -1 (message:
+ * rr_dqn_last_error) and launch nothing for: a null handle or required pointer, a partly-null metadata group, rows outside 1 .. 1<<22,
+ * frame_bytes not a multiple of 16 in 16 .. 1 MiB, src_row_stride not a multiple of 16 in frame_bytes .. 1<<32, a src / frames / state /
+ * next_state that is not 16-byte aligned, slots outside 2 .. 1<<31, head < 0.
+ *
+ * rr_frames_push: ONE launch copies row i's frame_bytes bytes from src + i * src_row_stride into slot head % slots (16-byte loads and
+ * stores) and writes the row's four metadata words.  The newest frame of a stacked observation [rows, 3 * stack, 64, 64] is taken in place:
+ * point src at its last three planes and pass the observation's row stride.  first [rows] (NULL: every row is first); action, reward,
+ * done, valid: each [rows], all NULL (action 0, reward 0, flags 0: a push that only records frames) or all given; flags = (valid ? 1 : 0)
+ * | (done ? 2 : 0).  Every byte of the slot's five arrays is written, nothing outside the slot; of the ring only `age` of slot
+ * (head - 1) % slots is read. */
+int rr_frames_push(rr_dqn *dqn, const uint8_t *src, int64_t src_row_stride, const uint8_t *first, const int32_t *action, const float *reward,
+                   const uint8_t *done, const uint8_t *valid, int32_t rows, int64_t frame_bytes, int64_t slots, int64_t head,
+                   uint8_t *frames, uint8_t *age, int32_t *action_ring, float *reward_ring, uint8_t *flags, void *stream);
+/* rr_frames_sample: `batch` transitions out of the ring in one launch.  Per sample b:
+ *   index == NULL (draw): attempts a = 0 .. 15 draw w = philox4x32_10(counter {b, call, 0x5A3E, a}, key = seed: low word, high word);
+ *     k = lo + (((uint64)w[0] * (head - lo)) >> 32), row = ((uint64)w[1] * rows) >> 32.  The lowest a whose flags[k][row] has bit 0 set
+ *     wins; none of the 16: ok[b] = 0.  Pass a fresh `call` every time.
+ *   index [batch, 2] = (k, row): taken as it stands; a k outside the window, a row outside 0 .. rows-1 or a clear bit 0 give ok[b] = 0
+ *     (such a value is never used as an index).
+ *   ok[b] = 1: state / next_state [batch, stack, frame_bytes] = the two stacks as defined above, action, reward, terminal (0 / 1) of the
+ *     transition, picked [batch, 2] (nullable) = (k, row).  ok[b] = 0: both stacks zero, action 0, reward 0, terminal 0, picked (-1, -1).
+ * Every output element of rows 0 .. batch-1 is written, no row at or beyond batch is touched; at most stack + 1 frames are read per sample
+ * for the 2 * stack it writes.  Also refused (-1): stack outside 1 .. 8, slots < stack + 1, batch outside 1 .. 1<<20, and in draw mode an
+ * empty window (head - lo < 1). */
+int rr_frames_sample(rr_dqn *dqn, const uint8_t *frames, const uint8_t *age, const int32_t *action_ring, const float *reward_ring,
+                     const uint8_t *flags, int32_t rows, int64_t frame_bytes, int64_t slots, int64_t head, int32_t stack, int32_t batch,
+                     const int64_t *index, uint64_t seed, uint32_t call, uint8_t *state, uint8_t *next_state, int32_t *action, float *reward,
+                     uint8_t *terminal, uint8_t *ok, int64_t *picked, void *stream);
+
 /* Introspection used by bench.py for the roofline line: bytes of the per-arena HBM record, and how many lanes of
  * a wavefront work on one arena (64 = one wavefront per arena; smaller = several arenas packed per wavefront). */
 int rr_state_bytes_per_env(const rr_env *env, int64_t *bytes);

@@ -4,7 +4,7 @@ Product = the HIP library (csrc/, built in-tree as libroborugby_amd.so) behind t
 include/roborugby_amd.h, plus this thin Python mirror of the reference's gym.Env surface."""
 from .config import PRESETS, Preset  # noqa: F401
 
-__all__ = ["PRESETS", "Preset", "BatchedRoboRugbyEnv", "RoboRugbyEnv", "make", "Direction", "DebugInfo", "ShardedPipeline", "PixelObservation"]
+__all__ = ["PRESETS", "Preset", "BatchedRoboRugbyEnv", "RoboRugbyEnv", "make", "Direction", "DebugInfo", "ShardedPipeline", "PixelObservation", "FrameReplay"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an env is actually used
@@ -17,4 +17,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an env is
     if name == "PixelObservation":
         from .pixels import PixelObservation
         return PixelObservation
+    if name == "FrameReplay":
+        from .frame_replay import FrameReplay
+        return FrameReplay
     raise AttributeError(name)

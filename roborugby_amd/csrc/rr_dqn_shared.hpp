@@ -1,9 +1,16 @@
 // rr_dqn_shared.hpp -- what the translation units behind the rr_dqn handle share (rr_dqn.hip: the lidar agent's fused kernels;
 // rr_cnn.hip: the pixel agent's forward): the handle itself, the error string's setter and the epsilon-greedy draw, so that
 // rr_dqn_act and rr_cnn_act explore the same rows with the same actions under one (seed, call).
+// The handle, the setter's declaration and the Philox rounds are plain C++ as well: csrc/rr_frames.hpp's host emulation includes this.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define RR_DQN_HD __host__ __device__ __forceinline__
+#else
+#define RR_DQN_HD inline
+#endif
 
 struct rr_dqn {
     int device, nwg;
@@ -17,7 +24,7 @@ struct rr_dqn {
 // sets the string rr_dqn_last_error returns (thread-local, rr_dqn.hip) and hands `code` back
 __attribute__((visibility("hidden"))) int rr_dqn_fail(int code, const char *msg);
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+RR_DQN_HD void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
     for (int r = 0; r < 10; r++) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
         const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
@@ -25,6 +32,7 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
 }
+#if defined(__HIPCC__)
 // the action of row `row` in call `call`: the greedy one, or (np.random.random() <= epsilon: explore) a uniform one
 __device__ __forceinline__ int epsilon_greedy(int best, int row, uint32_t call, uint64_t seed, float epsilon) {
     if (epsilon > 0.0f) {
@@ -34,3 +42,4 @@ __device__ __forceinline__ int epsilon_greedy(int best, int row, uint32_t call, 
     }
     return best;
 }
+#endif

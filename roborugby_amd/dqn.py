@@ -92,7 +92,7 @@ class _ReplayAgent:
     PERMUTE_LIMIT = 1 << 20  # sample without replacement (reference: np.random.choice(replace=False)) while a permutation is cheap
 
     def __init__(self, make_net, obs_shape, obs_dtype, gamma, epsilon, batch_size, n_actions, max_mem_size, eps_end, eps_dec,
-                 target_update_freq, device, seed):
+                 target_update_freq, device, seed, dense_memory=True):
         self.gamma, self.epsilon, self.eps_end, self.eps_dec = gamma, epsilon, eps_end, eps_dec
         self.n_actions, self.mem_size, self.batch_size = n_actions, int(max_mem_size), int(batch_size)
         self.target_update_freq = int(target_update_freq)
@@ -109,11 +109,13 @@ class _ReplayAgent:
         self.Q_eval = make_net()
         self.Q_target = copy.deepcopy(self.Q_eval)
         m, d = self.mem_size, self.device
-        self.state_memory = torch.zeros((m,) + tuple(obs_shape), dtype=obs_dtype, device=d)
-        self.new_state_memory = torch.zeros((m,) + tuple(obs_shape), dtype=obs_dtype, device=d)
-        self.action_memory = torch.zeros(m, dtype=torch.int64, device=d)
-        self.reward_memory = torch.zeros(m, dtype=torch.float32, device=d)
-        self.terminal_memory = torch.zeros(m, dtype=torch.bool, device=d)
+        self.state_memory = self.new_state_memory = self.action_memory = self.reward_memory = self.terminal_memory = None
+        if dense_memory:  # (a subclass with a replay of its own asks for none)
+            self.state_memory = torch.zeros((m,) + tuple(obs_shape), dtype=obs_dtype, device=d)
+            self.new_state_memory = torch.zeros((m,) + tuple(obs_shape), dtype=obs_dtype, device=d)
+            self.action_memory = torch.zeros(m, dtype=torch.int64, device=d)
+            self.reward_memory = torch.zeros(m, dtype=torch.float32, device=d)
+            self.terminal_memory = torch.zeros(m, dtype=torch.bool, device=d)
         self._dqn = None
 
     def _open_handle(self, fused, can_fuse, needs):
@@ -485,19 +487,42 @@ class PixelDQNAgent(_ReplayAgent):
     """BatchedDQNAgent's surface on the pixels of PixelObservation(size=64, stack=channels / 3).  Acting -- every row, every step -- is
     rr_cnn_act (one HIP kernel on the bf16 matrix cores, csrc/rr_cnn.hip) where it applies: on the GPU, contiguous uint8 rows, channels
     in {3, 6, 9, 12}, 8 actions; anything else, and fused=False, goes through the torch module.  Learning is PyTorch autograd on the same
-    parameters (MSE on r + gamma max Q_target, Adam, target sync and the epsilon schedule: _ReplayAgent's), the replay ring holds
-    uint8 frames and is written with torch indexing: 2 * channels * 4096 + 13 bytes per transition."""
+    parameters (MSE on r + gamma max Q_target, Adam, target sync and the epsilon schedule: _ReplayAgent's).
+    replay="dense" (the default): the replay ring holds both stacked observations of a transition as uint8 frames and is written with torch
+    indexing (store_transition): 2 * channels * 4096 + 13 bytes per transition.
+    replay="frames": a FrameReplay (frame_replay.py; rr_frames_push / rr_frames_sample) of `replay_rows` rows x `replay_slots` vector steps
+    that holds every frame once, 12,298 bytes per transition; no dense observation memory is allocated.  The loop calls
+    store_step(pixels, action, reward, done, valid, first) once per vector step (and once without a transition after a reset); learn()
+    draws its batch with rr_frames_sample and averages the same TD loss over the rows the sampler found a transition for.  mem_size is the
+    replay's capacity.  mem_cntr advances by `replay_rows` per push that carries transitions: re-placement rows -- at most one per episode
+    and row -- are COUNTED, because telling them apart would take a host read per step (the schedules run that little ahead)."""
     FUSED_CHANNELS = (3, 6, 9, 12)
     PERMUTE_LIMIT = math.inf  # always a permutation: a ring of frames never grows to where one costs
 
     def __init__(self, channels=12, gamma=.99, epsilon=1.0, lr=.0005, batch_size=256, n_actions=8, max_mem_size=65536, eps_end=0.2,
-                 eps_dec=.999997, target_update_freq=100000, device="cpu", seed=0, fused=None):
+                 eps_dec=.999997, target_update_freq=100000, device="cpu", seed=0, fused=None, replay="dense", replay_rows=None,
+                 replay_slots=None):
         self.channels = int(channels)
+        if replay not in ("dense", "frames"):
+            raise ValueError("PixelDQNAgent(replay=...): 'dense' or 'frames'")
+        self.replay_kind, self.replay = replay, None
         super().__init__(lambda: PixelQNetwork(self.channels, n_actions).to(device), (self.channels, 64, 64), torch.uint8, gamma, epsilon,
-                         batch_size, n_actions, max_mem_size, eps_end, eps_dec, target_update_freq, device, seed)
+                         batch_size, n_actions, max_mem_size, eps_end, eps_dec, target_update_freq, device, seed, dense_memory=replay == "dense")
         self.optimizer = torch.optim.Adam(self.Q_eval.parameters(), lr=lr)
         can_fuse = self.device.type == "cuda" and self.channels in self.FUSED_CHANNELS and n_actions == 8
         self._open_handle(fused, can_fuse, "a GPU, 3 / 6 / 9 / 12 channels and 8 actions")
+        if replay == "frames":
+            from .frame_replay import FrameReplay
+            if self.device.type != "cuda" or self.channels % 3 or replay_rows is None or replay_slots is None:
+                raise ValueError("PixelDQNAgent(replay='frames') needs a GPU, channels = 3 * stack, replay_rows and replay_slots")
+            self.replay = FrameReplay(replay_rows, replay_slots, self.channels // 3, device=self.device, seed=seed, dqn=self._dqn)
+            self.mem_size = self.replay.capacity
+            self._sampled = None
+
+    def close(self):
+        if self.replay is not None:
+            self.replay.close()
+        super().close()
 
     def _rows(self, pixels):
         if pixels.dim() == 5:  # PixelObservation with several robots: [N, R, C, 64, 64], a row per (arena, robot)
@@ -536,8 +561,43 @@ class PixelDQNAgent(_ReplayAgent):
         return out
 
     @torch.no_grad()
+    def store_step(self, pixels, action=None, reward=None, done=None, valid=None, first=None):
+        """replay="frames": one vector step into the FrameReplay -- the observation AFTER the step (its newest frame is stored), the action
+        that led to it, reward, done, valid (the rows whose step was a transition) and first (the rows whose stack restarted: WAS_RESET).
+        With only `pixels`: the observation after a reset / restart, which ends no transition and starts every stack over."""
+        if self.replay is None:
+            raise RuntimeError("store_step belongs to replay='frames'; the dense replay takes store_transition")
+        if action is None:
+            self.replay.restart()
+        self.replay.push(pixels, first, action, reward, done, valid)
+        if action is not None:
+            self.mem_cntr += self.replay.rows
+
+    def _learn_frames(self, max_mem):
+        """_learn_core on a batch of rr_frames_sample: the TD loss averaged over the rows with ok, sum(ok * err^2) / max(sum(ok), 1) --
+        F.mse_loss whenever every row is ok"""
+        self._sampled = self.replay.sample(self.batch_size, out=self._sampled)
+        state, state_, action, reward, terminal, ok = self._sampled
+        self.optimizer.zero_grad(set_to_none=False)
+        q_eval = self.Q_eval(state).gather(1, action.long().view(-1, 1)).squeeze(1)
+        with torch.no_grad():
+            q_next = self.Q_target(state_).masked_fill(terminal.view(-1, 1), 0.0)
+            q_target = reward + self.gamma * q_next.max(dim=1)[0]
+            w = ok.float()
+        loss = (w * (q_eval - q_target) ** 2).sum() / w.sum().clamp(min=1.0)
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach()
+
+    def _learn_step(self, max_mem):
+        return self._learn_frames(max_mem) if self.replay is not None else self._learn_core(max_mem)
+
+    @torch.no_grad()
     def store_transition(self, state, action, reward, state_, done, valid=None):
         """Appends the rows with valid=True (None: all) to the ring, in row order"""
+        if self.replay is not None:
+            raise RuntimeError("PixelDQNAgent(replay='frames') stores whole vector steps: call store_step(pixels, action, reward, done, "
+                               "valid, first), not store_transition")
         rows = self._compact(self._rows(state), action, reward, self._rows(state_), done, valid)
         if rows[0].shape[0] > self.mem_size:
             raise ValueError(f"{rows[0].shape[0]} transitions in one call do not fit a replay ring of {self.mem_size}")
@@ -906,7 +966,7 @@ def train_hive(num_envs=65536, steps=300, preset="G", robots=None, opponents="og
 
 def train_pixels(num_envs=4096, steps=300, stack=4, span=400.0, mem_size=65536, device="cuda:0", seed=0, checkpoint=None, resume=None,
                  log_every=50, learn=True, updates_per_step=1, batch_size=256, dtype="f64", eps_dec=.999997, eps_end=0.2,
-                 target_sync_vector_steps=64, out=None, step_budget_clocks=0, fused=None):
+                 target_sync_vector_steps=64, out=None, step_budget_clocks=0, fused=None, replay="dense"):
     """train()'s loop on pixels: preset T seen through PixelObservation(env, robots=0, size=64, stack=stack, span=span), the agent a
     PixelDQNAgent.  Per vector step, serial on one stream: choose_action (rr_cnn_act: one launch for every arena) -> env.step + the new
     frames -> store_transition of the rows that were transitions (not re-placements, as in train()) -> updates_per_step x learn()
@@ -914,6 +974,10 @@ def train_pixels(num_envs=4096, steps=300, stack=4, span=400.0, mem_size=65536, 
     The replay ring holds both observations of a transition as uint8 frames: 2 * 3 * stack * 4096 bytes = 96 KB per transition at
     stack 4, 6.4 GB at the default mem_size of 65,536 (24 KB and 1.6 GB at stack 1).  The observation before the step is copied once per
     step (PixelObservation overwrites its buffer): num_envs * 48 KB at stack 4.
+    replay="frames": the FrameReplay instead (PixelDQNAgent) -- every frame stored once, 12,298 bytes per transition, slots =
+    ceil(mem_size / num_envs) + stack so that mem_size keeps meaning "transitions held"; a vector step is one rr_frames_push of the new
+    frames (no copy of the observation before the step, no compaction, no host read) and learn() draws with rr_frames_sample.  The
+    result also names replay, replay_bytes_per_transition and replay_capacity.
     The budgeted step is not wired to pixels: step_budget_clocks != 0 is refused."""
     import roborugby_amd as rr
     from .pixels import PixelObservation
@@ -923,9 +987,13 @@ def train_pixels(num_envs=4096, steps=300, stack=4, span=400.0, mem_size=65536, 
         raise ValueError("train_pixels: stack in 1..4 (the network takes 3, 6, 9 or 12 channels)")
     env = rr.make("RoboRugbySimpleDuel-v3", num_envs=num_envs, preset="T", device=device, seed=seed, dtype=dtype)
     B = int(batch_size)
+    if replay not in ("dense", "frames"):
+        raise ValueError("train_pixels(replay=...): 'dense' or 'frames'")
+    frames = replay == "frames"
     agent = PixelDQNAgent(channels=3 * int(stack), batch_size=B, n_actions=env.action_space.n, device=device, seed=seed,
                           max_mem_size=mem_size, target_update_freq=max(100000, target_sync_vector_steps * num_envs),
-                          eps_dec=eps_dec, eps_end=eps_end, fused=fused)
+                          eps_dec=eps_dec, eps_end=eps_end, fused=fused, replay=replay, replay_rows=num_envs if frames else None,
+                          replay_slots=-(-int(mem_size) // num_envs) + int(stack) if frames else None)
     view = PixelObservation(env, robots=0, size=64, stack=int(stack), span=span)
     if resume:
         ck = torch.load(resume, map_location=device)
@@ -938,16 +1006,23 @@ def train_pixels(num_envs=4096, steps=300, stack=4, span=400.0, mem_size=65536, 
     t0 = time.perf_counter()
     score_sum = torch.zeros(num_envs, device=device)
     real_rows = torch.zeros((), dtype=torch.int64, device=device)
-    before = torch.empty_like(pixels)
+    if frames and learn:
+        agent.store_step(pixels)  # the observation every first transition starts from
+    if not frames:
+        before = torch.empty_like(pixels)
     for i in range(steps):
         action = agent.choose_action(pixels)
-        before.copy_(pixels)
+        if not frames:
+            before.copy_(pixels)
         pixels, reward, done, info = view.step(action.view(-1, 1))
         real = (info.status & (STATUS_WAS_RESET | STATUS_NOT_READY)) == 0  # a call that only re-placed the arena is not a transition
         score_sum += reward
         real_rows += real.sum()
         if learn:
-            agent.store_transition(before, action, reward, pixels, done, valid=real)
+            if frames:
+                agent.store_step(pixels, action, reward, done, real, first=(info.status & STATUS_WAS_RESET) != 0)
+            else:
+                agent.store_transition(before, action, reward, pixels, done, valid=real)
             for _ in range(updates_per_step):
                 agent.learn()
         if log_every and (i + 1) % log_every == 0:
@@ -959,7 +1034,9 @@ def train_pixels(num_envs=4096, steps=300, stack=4, span=400.0, mem_size=65536, 
     res = _train_result(agent, env, num_envs * steps, dt, steps, int(real_rows.item()), 0, updates_per_step if learn else 0, num_envs, False,
                         eps_dec, eps_end, False, float(score_sum.mean() / max(steps, 1)), "T", dtype, [])
     res.update(stack=int(stack), span=float(span), fused_act=bool(agent.fused),
-               loss=float(agent.last_loss) if agent.last_loss is not None else None)
+               loss=float(agent.last_loss) if agent.last_loss is not None else None, replay=replay,
+               replay_bytes_per_transition=agent.replay.bytes_per_transition if frames else 2 * agent.channels * 4096 + 13,
+               replay_capacity=agent.mem_size)
     agent.close()
     env.close()
     if out:
@@ -1000,12 +1077,16 @@ def main():
                     help="train the convolutional agent on preset T's egocentric 64 x 64 frames (PixelObservation); acting is rr_cnn_act "
                          "(--num-envs, default 4096 here; --steps, --checkpoint, --resume, --updates-per-step, --batch-size, --pixel-stack)")
     ap.add_argument("--pixel-stack", type=int, default=4, help="--train-pixels: frames per observation (1..4; 3 channels each)")
+    ap.add_argument("--pixel-replay", default="dense", choices=["dense", "frames"],
+                    help="--train-pixels: the replay -- dense (both stacked observations of every transition) or frames (FrameReplay: every "
+                         "frame once, rr_frames_push / rr_frames_sample)")
     a = ap.parse_args()
     if a.train_pixels:
         envs = a.num_envs if a.num_envs != ap.get_default("num_envs") else 4096  # (an observation is 48 KB at stack 4, not 44 bytes)
         res = train_pixels(envs, a.steps, a.pixel_stack, device=a.device, seed=a.seed, checkpoint=a.checkpoint, resume=a.resume,
                            log_every=a.log_every, learn=not a.no_learn, updates_per_step=a.updates_per_step, batch_size=a.batch_size or 256,
-                           eps_dec=a.eps_dec, out=a.out, step_budget_clocks=a.budget, fused=False if a.no_fused else None)
+                           eps_dec=a.eps_dec, out=a.out, step_budget_clocks=a.budget, fused=False if a.no_fused else None,
+                           replay=a.pixel_replay)
         print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
         return
     if a.play_hive:

@@ -11,6 +11,7 @@ static int g_dbg_scrub = 0; // overwrite everything but the persistent record wi
 #define RR_EMU_TRACE g_dbg_trace
 #include "../../roborugby_amd/csrc/rr_sim.hpp"
 #include "../../roborugby_amd/csrc/rr_extras.hpp"
+#include "emu_common.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -31,28 +32,18 @@ template <class C> struct Emu {
     uint32_t park_rng;
 };
 
+// emu_common.hpp's parameters, then what emu_create's caller chose
 template <typename R> static void fill_params(SimParams<R> &sp, double W, double H, int game_len, int game_mode,
                                               int time_limit, int auto_reset, uint64_t seed) {
-    derive_constants(sp, W, H);
+    emu_fill_params(sp, W, H);
     sp.game_len = game_len; sp.game_mode = game_mode; sp.time_limit = time_limit; sp.auto_reset = auto_reset & 1;
     sp.reset_on_fault = (auto_reset >> 1) & 1; // bit 1 of the flag word
-    sp.seed = seed; sp.arena_offset = 0; sp.memo = 1; sp.acc_external = 0;
+    sp.seed = seed;
 }
 
 template <class C> static void set_state(Emu<C> *e, const double *robots, const int32_t *ri, const double *balls, int step) {
-    using R = typename C::Real;
     Arena<C> &A = e->A;
-    for (int r = 0; r < C::NR; r++) {
-        const double *q = robots + 10 * r;
-        A.p.rcx[r] = (R)q[0]; A.p.rcy[r] = (R)q[1]; A.p.rl[r] = (R)q[2]; A.p.rrt[r] = (R)q[3]; A.p.rt[r] = (R)q[4];
-        A.p.rb[r] = (R)q[5]; A.p.rrot[r] = (R)q[6]; A.p.px[r] = (R)q[7]; A.p.py[r] = (R)q[8]; A.p.prot[r] = (R)q[9];
-        A.i.mc[r] = ri[3 * r]; A.i.thl[r] = ri[3 * r + 1]; A.i.thr[r] = ri[3 * r + 2];
-    }
-    for (int b = 0; b < C::NB; b++) {
-        const double *q = balls + 8 * b;
-        A.p.bcx[b] = (R)q[0]; A.p.bcy[b] = (R)q[1]; A.p.bl[b] = (R)q[2]; A.p.brt[b] = (R)q[3]; A.p.bt[b] = (R)q[4];
-        A.p.bb[b] = (R)q[5]; A.p.bvx[b] = (R)q[6]; A.p.bvy[b] = (R)q[7];
-    }
+    emu_put_state(A, robots, balls, ri);
     A.i.step = step;
     A.i.fault = 0;
     A.i.fzp = 0;
@@ -61,60 +52,30 @@ template <class C> static void set_state(Emu<C> *e, const double *robots, const 
 #endif
     derive(A, e->sp);
 }
-template <class C> static void get_state(Emu<C> *e, double *robots, int32_t *ri, double *balls, int32_t *step) {
-    Arena<C> &A = e->A;
-    for (int r = 0; r < C::NR; r++) {
-        double *q = robots + 10 * r;
-        q[0] = A.p.rcx[r]; q[1] = A.p.rcy[r]; q[2] = A.p.rl[r]; q[3] = A.p.rrt[r]; q[4] = A.p.rt[r]; q[5] = A.p.rb[r];
-        q[6] = A.p.rrot[r]; q[7] = A.p.px[r]; q[8] = A.p.py[r]; q[9] = A.p.prot[r];
-        ri[3 * r] = A.i.mc[r]; ri[3 * r + 1] = A.i.thl[r]; ri[3 * r + 2] = A.i.thr[r];
-    }
-    for (int b = 0; b < C::NB; b++) {
-        double *q = balls + 8 * b;
-        q[0] = A.p.bcx[b]; q[1] = A.p.bcy[b]; q[2] = A.p.bl[b]; q[3] = A.p.brt[b]; q[4] = A.p.bt[b]; q[5] = A.p.bb[b];
-        q[6] = A.p.bvx[b]; q[7] = A.p.bvy[b];
-    }
-    *step = A.i.step;
-}
 
-typedef Cfg<1, 0, 1, 0, double, 64> CT64;
-typedef Cfg<2, 2, 4, 4, double, 64> CG64;
-typedef Cfg<1, 0, 1, 0, float, 64> CT32;
-typedef Cfg<2, 2, 4, 4, float, 64> CG32;
-// narrow virtual waves: the same phases run in several rounds of VW lanes (what the packed GPU builds execute)
-typedef Cfg<1, 0, 1, 0, double, 4> CT64n;
-typedef Cfg<2, 2, 4, 4, double, 16> CG64n;
-// the duel shape (1+1 robots, 1+1 balls)
-typedef Cfg<1, 1, 1, 1, double, 64> CD64;
-typedef Cfg<1, 1, 1, 1, float, 64> CD32;
-typedef Cfg<1, 1, 1, 1, double, 4> CD64n;
-// a shape that is NOT one of the library's built ones (2+1 robots, 2+3 balls: odd counts, unequal teams): what build_shape_library
-// compiles on demand (roborugby_amd/build.py); one lane per entity needs 8 lanes
-typedef Cfg<2, 1, 2, 3, double, 64> CX64;
-typedef Cfg<2, 1, 2, 3, double, 8> CX64n;
-// ... and one that packs at FOUR lanes per arena (1 + 1 robots, 2 + 1 balls): the narrow phases' "fewer than eight lanes" variants with
-// more than one ball, a combination none of the built shapes has
-typedef Cfg<1, 1, 2, 1, double, 64> CY64;
-typedef Cfg<1, 1, 2, 1, double, 4> CY64n;
+// The built kinds: X(handle kind, name, NRH, NRG, NBP, NBN, precision, lanes per arena).
+//   n:    narrow virtual waves: the same phases run in several rounds of VW lanes (what the packed GPU builds execute)
+//   D:    the duel shape (1 + 1 robots, 1 + 1 balls)
+//   X:    a shape that is NOT one of the library's built ones (2 + 1 robots, 2 + 3 balls: odd counts, unequal teams): what
+//         build_shape_library compiles on demand (roborugby_amd/build.py); one lane per entity needs 8 lanes
+//   Y:    one that packs at FOUR lanes per arena (1 + 1 robots, 2 + 1 balls): the narrow phases' "fewer than eight lanes" variants with
+//         more than one ball, a combination none of the built shapes has
+#define EMU_KINDS(X, ...)                                                                                                           \
+    X(0, CT64, 1, 0, 1, 0, double, 64, __VA_ARGS__) X(1, CG64, 2, 2, 4, 4, double, 64, __VA_ARGS__)                                  \
+    X(2, CT32, 1, 0, 1, 0, float, 64, __VA_ARGS__) X(3, CG32, 2, 2, 4, 4, float, 64, __VA_ARGS__)                                    \
+    X(4, CT64n, 1, 0, 1, 0, double, 4, __VA_ARGS__) X(5, CG64n, 2, 2, 4, 4, double, 16, __VA_ARGS__)                                 \
+    X(6, CD64, 1, 1, 1, 1, double, 64, __VA_ARGS__) X(7, CD32, 1, 1, 1, 1, float, 64, __VA_ARGS__)                                   \
+    X(8, CD64n, 1, 1, 1, 1, double, 4, __VA_ARGS__)                                                                                  \
+    X(9, CX64, 2, 1, 2, 3, double, 64, __VA_ARGS__) X(10, CX64n, 2, 1, 2, 3, double, 8, __VA_ARGS__)                                 \
+    X(11, CY64, 1, 1, 2, 1, double, 64, __VA_ARGS__) X(12, CY64n, 1, 1, 2, 1, double, 4, __VA_ARGS__)
+#define EMU_TYPEDEF(k, name, a, b, c, d, R_, v_, ...) typedef Cfg<a, b, c, d, R_, v_> name;
+EMU_KINDS(EMU_TYPEDEF, 0)
 
 struct Handle { int kind; void *p; };
 
-#define DISPATCH(h, ...)                                                   \
-    switch ((h)->kind) {                                                   \
-    case 0: { auto *e = (Emu<CT64> *)(h)->p; typedef CT64 CC; __VA_ARGS__; } break; \
-    case 1: { auto *e = (Emu<CG64> *)(h)->p; typedef CG64 CC; __VA_ARGS__; } break; \
-    case 2: { auto *e = (Emu<CT32> *)(h)->p; typedef CT32 CC; __VA_ARGS__; } break; \
-    case 3: { auto *e = (Emu<CG32> *)(h)->p; typedef CG32 CC; __VA_ARGS__; } break; \
-    case 4: { auto *e = (Emu<CT64n> *)(h)->p; typedef CT64n CC; __VA_ARGS__; } break; \
-    case 5: { auto *e = (Emu<CG64n> *)(h)->p; typedef CG64n CC; __VA_ARGS__; } break; \
-    case 6: { auto *e = (Emu<CD64> *)(h)->p; typedef CD64 CC; __VA_ARGS__; } break; \
-    case 7: { auto *e = (Emu<CD32> *)(h)->p; typedef CD32 CC; __VA_ARGS__; } break; \
-    case 8: { auto *e = (Emu<CD64n> *)(h)->p; typedef CD64n CC; __VA_ARGS__; } break; \
-    case 9: { auto *e = (Emu<CX64> *)(h)->p; typedef CX64 CC; __VA_ARGS__; } break; \
-    case 10: { auto *e = (Emu<CX64n> *)(h)->p; typedef CX64n CC; __VA_ARGS__; } break; \
-    case 11: { auto *e = (Emu<CY64> *)(h)->p; typedef CY64 CC; __VA_ARGS__; } break; \
-    case 12: { auto *e = (Emu<CY64n> *)(h)->p; typedef CY64n CC; __VA_ARGS__; } break; \
-    }
+// runs the statements with e = the handle's Emu<CC> *
+#define EMU_CASE(k, name, a, b, c, d, R_, v_, h, ...) case k: { auto *e = (Emu<name> *)(h)->p; typedef name CC; __VA_ARGS__; } break;
+#define DISPATCH(h, ...) switch ((h)->kind) { EMU_KINDS(EMU_CASE, h, __VA_ARGS__) }
 
 extern "C" {
 void emu_debug_set_substeps(int k) { g_dbg_substeps = k; }
@@ -133,21 +94,8 @@ Handle *emu_create(int preset, int f32, double W, double H, int game_len, int ga
                    uint64_t seed) {
     Handle *h = new Handle;
     h->kind = preset == 4 ? (f32 == 2 ? 12 : 11) : preset == 3 ? (f32 == 2 ? 10 : 9) : preset == 2 ? 6 + f32 : preset + 2 * f32; // presets 3, 4 = X, Y (fp64 only)
-    switch (h->kind) {
-    case 11: h->p = calloc(1, sizeof(Emu<CY64>)); break;
-    case 12: h->p = calloc(1, sizeof(Emu<CY64n>)); break;
-    case 9: h->p = calloc(1, sizeof(Emu<CX64>)); break;
-    case 10: h->p = calloc(1, sizeof(Emu<CX64n>)); break;
-    case 6: h->p = calloc(1, sizeof(Emu<CD64>)); break;
-    case 7: h->p = calloc(1, sizeof(Emu<CD32>)); break;
-    case 8: h->p = calloc(1, sizeof(Emu<CD64n>)); break;
-    case 0: h->p = calloc(1, sizeof(Emu<CT64>)); break;
-    case 1: h->p = calloc(1, sizeof(Emu<CG64>)); break;
-    case 2: h->p = calloc(1, sizeof(Emu<CT32>)); break;
-    case 3: h->p = calloc(1, sizeof(Emu<CG32>)); break;
-    case 4: h->p = calloc(1, sizeof(Emu<CT64n>)); break;
-    default: h->p = calloc(1, sizeof(Emu<CG64n>)); break;
-    }
+#define EMU_ALLOC(k, name, a, b, c, d, R_, v_, ...) case k: h->p = calloc(1, sizeof(Emu<name>)); break;
+    switch (h->kind) { EMU_KINDS(EMU_ALLOC, 0) }
     DISPATCH(h, fill_params(e->sp, W, H, game_len, game_mode, time_limit, auto_reset, seed); (void)sizeof(CC);
              e->prog.n = 3; e->prog.id[0] = 1; e->prog.id[1] = 2; e->prog.id[2] = 3; e->custom_prog = false;
              for (int r = 0; r < CC::NR; r++) robot_set_clean_lane(e->A, e->sp, r, (typename CC::Real)0, (typename CC::Real)0,
@@ -162,7 +110,7 @@ void emu_set_state(Handle *h, const double *robots, const int32_t *ri, const dou
     DISPATCH(h, set_state<CC>(e, robots, ri, balls, step));
 }
 void emu_get_state(Handle *h, double *robots, int32_t *ri, double *balls, int32_t *step) {
-    DISPATCH(h, get_state<CC>(e, robots, ri, balls, step));
+    DISPATCH(h, emu_get_state(e->A, robots, balls, ri); *step = e->A.i.step); // (emu_common.hpp's, on the arena)
 }
 // centre of the reference's scratch rect (_rectBallInner): 1 if this build carries it (the parity build), 0 otherwise
 int emu_set_scratch_rect(Handle *h, const double *xy) {

@@ -4,6 +4,8 @@
 // never links or loads this.  With -DRR_RENDER_EGO_EMU_MAIN it is a stand-alone program over crafted arenas (for a sanitizer build: every
 // frame buffer is a heap block of exactly the frames' size).
 #include "../../roborugby_amd/csrc/rr_render.hpp"
+#define EMU_COMMON_RENDER // the records, the layout and the crafted arenas both render emulations use
+#include "emu_common.hpp"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -53,42 +55,20 @@ int render_ego_emu(int f32rec, int nr, int nrh, int nb, int nbp, double W, doubl
         height > 1024 || (S != 1 && S != 2 && S != 4) || !(span >= 16.0f && span <= 16384.0f) || !(ahead >= -8192.0f && ahead <= 8192.0f) ||
         (flags & ~(RENDER_EGO_RELATIVE | RENDER_EGO_PLANAR)) || !rgb)
         return -1;
-    const int stride = 10 * nr + 8 * nb;
-    const RenderLayout L = { 0, nr, 6 * nr, 10 * nr, 10 * nr + nb, stride, nr, nrh, nb, nbp, f32rec ? 0 : 1 };
+    const RenderLayout L = emu_render_layout(nr, nrh, nb, nbp, f32rec);
     const EgoView V = render_ego_view(W, H, width, height, S, span, ahead, flags);
-    std::vector<double> rd((size_t)n * stride);
-    for (int a = 0; a < n; a++) {
-        double *rec = rd.data() + (size_t)a * stride;
-        for (int r = 0; r < nr; r++) for (int f = 0; f < 10; f++) rec[f * nr + r] = robots[((size_t)a * nr + r) * 10 + f];
-        for (int b = 0; b < nb; b++) for (int f = 0; f < 8; f++) rec[10 * nr + f * nb + b] = balls[((size_t)a * nb + b) * 8 + f];
-    }
-    if (f32rec) {
-        std::vector<float> rf(rd.begin(), rd.end());
-        render_ego_grid(L, V, rf.data(), n, arenas, viewers, m, rgb);
-    } else {
-        render_ego_grid(L, V, rd.data(), n, arenas, viewers, m, rgb);
-    }
+    emu_render_records(f32rec, n, nr, nb, robots, balls, [&](const void *recs) { render_ego_grid(L, V, recs, n, arenas, viewers, m, rgb); });
     return 0;
 }
 }
 
 #ifdef RR_RENDER_EGO_EMU_MAIN
-// Crafted arenas of G's shape (2 + 2 robots, 4 + 4 balls, 800 x 800): viewers at rot 0, 45, 90, 200, 270 and 359.999, next to a wall, in
-// a corner and in a goal, a ball on the viewer, a consumed ball, a NaN viewer; frames of arenas and robots out of range.
+// emu_common.hpp's crafted arenas seen by every kind of viewer in them (at each rotation, next to a wall, in a corner and in a goal, a
+// ball on the viewer, a NaN viewer), and frames of arenas and robots out of range.
 int main() {
-    const int nr = 4, nb = 8, n = 3;
-    const double nan = strtod("nan", nullptr);
-    std::vector<double> robots((size_t)n * nr * 10, 0.0), balls((size_t)n * nb * 8, 0.0);
-    const double R[n][nr][3] = { { { 300.25, 400.5, 0 }, { 310.75, 410.125, 45 }, { 500.5, 200.25, 90 }, { 120.3, 119.6, 359.999 } },
-                                 { { 700.4, 690.2, 30 }, { nan, 300, 10 }, { 20.5, 780.5, 200 }, { 400, 400, nan } },
-                                 { { 11.5, 21.5, 0 }, { 788.5, 778.5, 180 }, { 400.1, 21, 270 }, { 21, 400.9, 90 } } };
-    const double B[n][nb][2] = { { { 300.25, 400.5 }, { 3, 300.5 }, { -1000, 50 }, { 600.5, 600.5 }, { 602.5, 603 }, { 797, 100 }, { 100, 797.5 }, { 50.5, 60.5 } },
-                                 { { 700, 690 }, { nan, 5 }, { 7, 7 }, { 793, 793 }, { 400, -3 }, { 400, 803 }, { 150.2, 89.9 }, { 650, 710 } },
-                                 { { 7.5, 7.5 }, { 792.5, 792.5 }, { 400, 400 }, { 401, 401 }, { 402, 402 }, { 403, 403 }, { 404, 404 }, { 405, 405 } } };
-    for (int a = 0; a < n; a++) {
-        for (int r = 0; r < nr; r++) { double *q = &robots[((size_t)a * nr + r) * 10]; q[0] = R[a][r][0]; q[1] = R[a][r][1]; q[6] = R[a][r][2]; }
-        for (int b = 0; b < nb; b++) { double *q = &balls[((size_t)a * nb + b) * 8]; q[0] = B[a][b][0]; q[1] = B[a][b][1]; }
-    }
+    const int nr = EMU_CRAFTED_NR, nb = EMU_CRAFTED_NB, n = EMU_CRAFTED_N;
+    std::vector<double> robots, balls;
+    emu_crafted_arenas(robots, balls);
     const int m = 12;
     //                       zero frames: arena -1, arena 3, robot -1, robot 4, NaN x, NaN rot, INT32 min / max
     const int32_t arenas[m] = { 2, 0, 0, 1, 2, 2, -1, 3, 0, 0, 1, 1 }, viewers[m] = { 0, 3, 1, 2, 2, 1, 0, 0, -1, 4, 1, 3 };

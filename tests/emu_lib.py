@@ -4,45 +4,30 @@ The emulation compiles the kernel's own source (roborugby_amd/csrc/rr_sim.hpp) w
 lane-parallel phase as a 64-iteration loop.  It checks phase logic on CPU; it is never a product path."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import emu_build as eb
 import oracle_lib as ol
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, "emu", "librr_emu.so")
-SO_EXACT = os.path.join(HERE, "emu", "librr_emu_exact.so")  # the same source with -DRR_EXACT_TRIG=1 (the exact-trig parity build)
-SRC = [os.path.join(HERE, "emu", "rr_emu.cpp"), os.path.join(ol.REPO, "roborugby_amd", "csrc", "rr_sim.hpp")]
+SO, SO_EXACT = eb.LIBS["emu"].so, eb.LIBS["emu_exact"].so  # the second: the same source with -DRR_EXACT_TRIG=1 (the exact-trig parity build)
 
 
 def build(exact=False):
-    so = SO_EXACT if exact else SO
-    if not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in SRC):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-ffp-contract=off", "-std=c++17", "-shared"] + (["-DRR_EXACT_TRIG=1"] if exact else [])
-                              + ["-o", so, SRC[0]])
-    return so
-
-
-_lib = None
-_libs = {}
+    return eb.build(eb.LIBS["emu_exact" if exact else "emu"])
 
 
 # RR_EMU_EXACT=1: every test that does not say otherwise runs against the parity build (tests/test_parity_build.py re-runs the
 # shortcut-equivalence suites that way)
 DEFAULT_EXACT = bool(int(os.environ.get("RR_EMU_EXACT", "0")))
+_libs = {}  # {exact: bound library}
 
 
 def lib(exact=None):
-    exact = DEFAULT_EXACT if exact is None else exact
-    global _lib
-    if exact:
-        if True not in _libs:
-            _libs[True] = _bind(C.CDLL(build(True)))
-        return _libs[True]
-    if _lib is None:
-        _lib = _bind(C.CDLL(build()))
-    return _lib
+    exact = DEFAULT_EXACT if exact is None else bool(exact)
+    if exact not in _libs:
+        _libs[exact] = _bind(eb.load(eb.LIBS["emu_exact" if exact else "emu"]))
+    return _libs[exact]
 
 
 def _bind(L):
@@ -72,11 +57,11 @@ def _bind(L):
 
 
 def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+    return eb.ptr(a, C.c_double)
 
 
 def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
+    return eb.ptr(a, C.c_int32)
 
 
 class EmuEnv:
@@ -84,11 +69,10 @@ class EmuEnv:
         self._exact = DEFAULT_EXACT if exact is None else bool(exact)
         cfg = ol.PRESETS[preset]
         self.cfg = cfg
-        self.nr = cfg["nr_h"] + cfg["nr_g"]
-        self.nb = cfg["nb_p"] + cfg["nb_n"]
+        _, self.nr, _, self.nb = eb.counts(preset)
         # narrow=True: fp64 with VW = 4 (T, D) / 16 (G) lanes per arena, i.e. multi-round phases as in the packed builds
-        self.h = lib(self._exact).emu_create({"T": 0, "G": 1, "D": 2, "X": 3, "Y": 4}[ol.SHAPE.get(preset, preset)], 2 if narrow else int(f32), cfg["W"], cfg["H"], cfg["game_len"],
-                                  cfg["game_mode"], time_limit, int(auto_reset) | (int(reset_on_fault) << 1), seed)
+        self.h = lib(self._exact).emu_create(eb.PRESET_ID[preset], 2 if narrow else int(f32), cfg["W"], cfg["H"], cfg["game_len"],
+                                             cfg["game_mode"], time_limit, int(auto_reset) | (int(reset_on_fault) << 1), seed)
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -123,28 +107,25 @@ class EmuEnv:
         b = np.ascontiguousarray(bxyv, np.float64)
         lib(self._exact).emu_set_poses(self.h, _dp(r), _dp(b))
 
-    def step(self, actions):
-        a = np.ascontiguousarray(np.asarray(actions).reshape(-1), np.int32)
+    def _result(self, fn, *inputs, extra=()):
+        """fn(handle, inputs..., the five outputs, extra...) -> the step's dict"""
         obs, obs_g, rew, rew_g = np.zeros(11), np.zeros(11), np.zeros(1), np.zeros(1)
         done = np.zeros(1, np.uint8)
-        st = lib(self._exact).emu_step(self.h, _ip(a), len(a), _dp(obs), _dp(obs_g), _dp(rew), _dp(rew_g),
-                            done.ctypes.data_as(C.POINTER(C.c_uint8)))
+        st = int(fn(self.h, *inputs, _dp(obs), _dp(obs_g), _dp(rew), _dp(rew_g), eb.ptr(done, C.c_uint8), *extra))
         # status word: flags in bits 0-15, NaughtyBots' robot set in bits 16+
         return dict(obs=obs, obs_g=obs_g, reward=float(rew[0]), reward_g=float(rew_g[0]), done=bool(done[0]),
-                    status=int(st) & 0xFFFF, naughty=(int(st) >> 16) & 0xFF)
+                    status=st & 0xFFFF, naughty=(st >> 16) & 0xFF)
+
+    def step(self, actions):
+        a = np.ascontiguousarray(np.asarray(actions).reshape(-1), np.int32)
+        return self._result(lib(self._exact).emu_step, _ip(a), len(a))
 
     def step_budget(self, actions, park_mod=3):
         """The budgeted step of the kernel source (rr_sim.hpp: ParkCtx): parks at pseudo-random sub-step boundaries (1 in park_mod).
         Returns None while the step is parked (status NOT_READY: nothing was written), else the usual dict."""
         a = np.ascontiguousarray(np.asarray(actions).reshape(-1), np.int32)
-        obs, obs_g, rew, rew_g = np.zeros(11), np.zeros(11), np.zeros(1), np.zeros(1)
-        done = np.zeros(1, np.uint8)
-        st = lib(self._exact).emu_step_budget(self.h, _ip(a), len(a), _dp(obs), _dp(obs_g), _dp(rew), _dp(rew_g),
-                                   done.ctypes.data_as(C.POINTER(C.c_uint8)), int(park_mod))
-        if int(st) & 16384:
-            return None
-        return dict(obs=obs, obs_g=obs_g, reward=float(rew[0]), reward_g=float(rew_g[0]), done=bool(done[0]),
-                    status=int(st) & 0xFFFF, naughty=(int(st) >> 16) & 0xFF)
+        r = self._result(lib(self._exact).emu_step_budget, _ip(a), len(a), extra=(int(park_mod),))
+        return None if r["status"] & 16384 else r
 
     def park_seed(self, seed):
         lib(self._exact).emu_park_seed(self.h, int(seed) & 0xFFFFFFFF)
@@ -160,12 +141,7 @@ class EmuEnv:
 
     def step_thrust(self, thrust):
         t = np.ascontiguousarray(np.asarray(thrust, np.float32).reshape(-1))
-        obs, obs_g, rew, rew_g = np.zeros(11), np.zeros(11), np.zeros(1), np.zeros(1)
-        done = np.zeros(1, np.uint8)
-        st = lib(self._exact).emu_step_thrust(self.h, t.ctypes.data_as(C.POINTER(C.c_float)), len(t) // 2, _dp(obs), _dp(obs_g),
-                                   _dp(rew), _dp(rew_g), done.ctypes.data_as(C.POINTER(C.c_uint8)))
-        return dict(obs=obs, obs_g=obs_g, reward=float(rew[0]), reward_g=float(rew_g[0]), done=bool(done[0]),
-                    status=int(st) & 0xFFFF, naughty=(int(st) >> 16) & 0xFF)
+        return self._result(lib(self._exact).emu_step_thrust, eb.ptr(t, C.c_float), len(t) // 2)
 
     def set_goal_scoring(self, on=True):
         lib(self._exact).emu_set_goal_scoring(self.h, int(on))

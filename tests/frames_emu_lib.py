@@ -1,52 +1,33 @@
 """ctypes binding of the host-emulated frame-replay kernels (tests/emu/rr_frames_emu.cpp: g++ build of csrc/rr_frames.hpp) -- test harness
 only."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build as eb
 import frames_ref as fr
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-SO = os.path.join(HERE, "emu", "librr_frames_emu.so")
-CSRC = os.path.join(REPO, "roborugby_amd", "csrc")
-SRC = [os.path.join(HERE, "emu", "rr_frames_emu.cpp")] + [os.path.join(CSRC, f) for f in ("rr_frames.hpp", "rr_dqn_shared.hpp")]
-FLAGS = ["-O2", "-std=c++17"]
+LIB = eb.LIBS["frames"]
+_vp = C.c_void_p
+_p = eb.ptr  # an array's data as a void *, None for None
 
 
 def build():
-    if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(s) for s in SRC):
-        tmp = SO + f".tmp{os.getpid()}"
-        subprocess.check_call(["g++"] + FLAGS + ["-fPIC", "-shared", "-o", tmp, SRC[0]])
-        os.replace(tmp, SO)
-    return SO
+    return eb.build(LIB)
 
 
 def build_program(path, extra=()):
     """the same source as a stand-alone program with its own main (rings pushed past three wraps and sampled both ways, every block a heap
     block of exactly its size), e.g. with extra=("-fsanitize=address,undefined", "-g")"""
-    subprocess.check_call(["g++"] + FLAGS + list(extra) + ["-DRR_FRAMES_EMU_MAIN", "-o", path, SRC[0]])
-    return path
-
-
-_lib = None
-_vp = C.c_void_p
+    return eb.build_program(LIB, path, extra)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.frames_push_emu.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp]
-        _lib.frames_sample_emu.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_uint64,
-                                           C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    return _lib
-
-
-def _p(a):
-    return None if a is None else _vp(a.ctypes.data)
+    L = eb.load(LIB)
+    L.frames_push_emu.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp]
+    L.frames_sample_emu.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_uint64,
+                                    C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    return L
 
 
 def push(ring, src, stride=None, first=None, action=None, reward=None, done=None, valid=None, offset=0):

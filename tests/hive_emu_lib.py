@@ -1,57 +1,38 @@
 """ctypes binding of the host-emulated hive-mind kernel (tests/emu/rr_hive_emu.cpp) -- test harness only -- and the numpy
 restatement of the greedy assignment rule the CPU and GPU tests compare with."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build as eb
 import oracle_lib as ol
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, "emu", "librr_hive_emu.so")
-CSRC = os.path.join(ol.REPO, "roborugby_amd", "csrc")
-SRC = [os.path.join(HERE, "emu", "rr_hive_emu.cpp")] + [os.path.join(CSRC, f) for f in ("rr_hive.hpp", "rr_extras.hpp", "rr_sim.hpp")]
-PRESET_ID = {"T": 0, "G": 1, "D": 2, "X": 3}
-# lanes per arena the emulation is built for: the product's width of the shape (csrc/rr_kstep.hpp; X: build.shape_lanes), wider groups and 64
+# lanes per arena the tests run the emulation at (rows of EMU_HIVE_TABLE, tests/emu/emu_common.hpp): the product's width of the shape
+# (csrc/rr_kstep.hpp; X: build.shape_lanes), wider groups and 64
 LANES = {"T": (2, 4, 64), "G": (8, 16, 32, 64), "D": (4, 64), "X": (8, 64)}
-for _wide, _shape in ol.SHAPE.items():  # the non-square ids run their shape's build at their own W, H
-    PRESET_ID[_wide], LANES[_wide] = PRESET_ID[_shape], LANES[_shape]
+LANES.update({wide: LANES[shape] for wide, shape in ol.SHAPE.items()})  # the non-square ids run their shape's build at their own W, H
 
 
 def build():
-    if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(s) for s in SRC):
-        tmp = SO + f".tmp{os.getpid()}"
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-ffp-contract=off", "-std=c++17", "-shared", "-o", tmp, SRC[0]])
-        os.replace(tmp, SO)
-    return SO
-
-
-_lib = None
+    return eb.build(eb.LIBS["hive"])
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        _lib.hive_emu.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, C.c_uint32, C.c_int, ip, dp]
-    return _lib
+    L = eb.load(eb.LIBS["hive"])
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    L.hive_emu.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, C.c_uint32, C.c_int, ip, dp]
+    return L
 
 
 def hive_observe(preset, robots, balls, mask, kind, vw, f32=False):
     """robots [n,NR,10], balls [n,NB,8] (canonical layout) -> (assign int32 [n,NR], obs float64 [n,NR,11]) of the kernel source"""
     cfg = ol.PRESETS[preset]
-    nr, nb = cfg["nr_h"] + cfg["nr_g"], cfg["nb_p"] + cfg["nb_n"]
-    r = np.ascontiguousarray(robots, np.float64).reshape(-1, nr, 10)
-    b = np.ascontiguousarray(balls, np.float64).reshape(-1, nb, 8)
-    n = r.shape[0]
-    assert b.shape[0] == n
+    r, b = eb.canonical(preset, robots, balls)
+    n, nr = r.shape[:2]
     assign = np.full((n, nr), -7, np.int32)
     obs = np.full((n, nr, 11), np.nan)
-    rc = lib().hive_emu(PRESET_ID[preset], int(vw), int(f32), cfg["W"], cfg["H"], n, r.ctypes.data_as(C.POINTER(C.c_double)),
-                        b.ctypes.data_as(C.POINTER(C.c_double)), int(mask), int(kind), assign.ctypes.data_as(C.POINTER(C.c_int32)),
-                        obs.ctypes.data_as(C.POINTER(C.c_double)))
+    rc = lib().hive_emu(eb.PRESET_ID[preset], int(vw), int(f32), cfg["W"], cfg["H"], n, eb.ptr(r, C.c_double), eb.ptr(b, C.c_double), int(mask),
+                        int(kind), eb.ptr(assign, C.c_int32), eb.ptr(obs, C.c_double))
     assert rc == 0, (preset, vw, f32)
     return assign, obs
 

@@ -3,47 +3,27 @@ numpy restatement of the per-robot reward and of the validity rules (include/rob
 tests compare with."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
-import hive_emu_lib as he
+import emu_build as eb
 import oracle_lib as ol
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, "emu", "librr_hive_transition_emu.so")
-SRC = [os.path.join(HERE, "emu", "rr_hive_transition_emu.cpp")] + he.SRC[1:]
 WAS_RESET, NOT_READY, STEP_AFTER_DONE = 1024, 16384, 64
 NOT_STEPPED = WAS_RESET | NOT_READY | STEP_AFTER_DONE
+counts = eb.counts
 
 
 def build():
-    if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(s) for s in SRC):
-        tmp = SO + f".tmp{os.getpid()}"
-        # hive_emu_lib's flags + -fno-builtin: the rewards' distances are the reference's pow(x, 2.0) / pow(x, .5) and must stay the libm
-        # calls CPython makes (g++ would fold the former to x * x), as oracle/Makefile keeps them for the oracle
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-ffp-contract=off", "-fno-builtin", "-std=c++17", "-shared", "-o", tmp, SRC[0]])
-        os.replace(tmp, SO)
-    return SO
-
-
-_lib = None
+    return eb.build(eb.LIBS["hive_transition"])  # (its own library for its -fno-builtin: emu_build.LIBS says why)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
-        _lib.hive_transition_emu.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, dp, dp, C.c_uint32, C.c_int,
-                                             ip, ip, bp, dp, dp, bp, bp]
-    return _lib
-
-
-def counts(preset):
-    cfg = ol.PRESETS[preset]
-    return cfg["nr_h"], cfg["nr_h"] + cfg["nr_g"], cfg["nb_p"], cfg["nb_p"] + cfg["nb_n"]
+    L = eb.load(eb.LIBS["hive_transition"])
+    dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    L.hive_transition_emu.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, dp, dp, C.c_uint32, C.c_int,
+                                      ip, ip, bp, dp, dp, bp, bp]
+    return L
 
 
 def hive_transition(preset, robots0, balls0, robots1, balls1, mask, kind, assign, status, done, vw, f32=False):
@@ -52,13 +32,10 @@ def hive_transition(preset, robots0, balls0, robots1, balls1, mask, kind, assign
     -> (next_obs float64 [n,NR,11], reward float64 [n,NR], terminal uint8 [n,NR], valid uint8 [n,NR]); the outputs start as
     NaN / 255, so an element the kernel source does not write shows."""
     cfg = ol.PRESETS[preset]
-    _, nr, _, nb = counts(preset)
-    dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
-    r0 = np.ascontiguousarray(robots0, np.float64).reshape(-1, nr, 10)
-    n = r0.shape[0]
-    b0 = np.ascontiguousarray(balls0, np.float64).reshape(n, nb, 8)
-    r1 = np.ascontiguousarray(robots1, np.float64).reshape(n, nr, 10)
-    b1 = np.ascontiguousarray(balls1, np.float64).reshape(n, nb, 8)
+    r0, b0 = eb.canonical(preset, robots0, balls0)
+    n, nr = r0.shape[:2]
+    r1, b1 = eb.canonical(preset, robots1, balls1)
+    assert r1.shape[0] == n
     a = np.ascontiguousarray(assign, np.int32).reshape(n, nr)
     st = np.ascontiguousarray(status, np.int32).reshape(n)
     dn = np.ascontiguousarray(done, np.uint8).reshape(n)
@@ -66,10 +43,10 @@ def hive_transition(preset, robots0, balls0, robots1, balls1, mask, kind, assign
     rew = np.full((n, nr), np.nan)
     term = np.full((n, nr), 255, np.uint8)
     val = np.full((n, nr), 255, np.uint8)
-    rc = lib().hive_transition_emu(he.PRESET_ID[preset], int(vw), int(f32), cfg["W"], cfg["H"], n, r0.ctypes.data_as(dp), b0.ctypes.data_as(dp),
-                                   r1.ctypes.data_as(dp), b1.ctypes.data_as(dp), int(mask), int(kind), a.ctypes.data_as(ip),
-                                   st.ctypes.data_as(ip), dn.ctypes.data_as(bp), obs.ctypes.data_as(dp), rew.ctypes.data_as(dp),
-                                   term.ctypes.data_as(bp), val.ctypes.data_as(bp))
+    d, i, u8 = C.c_double, C.c_int32, C.c_uint8
+    rc = lib().hive_transition_emu(eb.PRESET_ID[preset], int(vw), int(f32), cfg["W"], cfg["H"], n, eb.ptr(r0, d), eb.ptr(b0, d), eb.ptr(r1, d),
+                                   eb.ptr(b1, d), int(mask), int(kind), eb.ptr(a, i), eb.ptr(st, i), eb.ptr(dn, u8), eb.ptr(obs, d), eb.ptr(rew, d),
+                                   eb.ptr(term, u8), eb.ptr(val, u8))
     assert rc == 0, (preset, vw, f32)
     return obs, rew, term, val
 

@@ -85,16 +85,29 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
     load_record(A, rec, irec);
     derive(A, sp);
     RR_STAMP(12);
+    // The constants the sub-step loop reads (wall tests, corner renormalisation, the balls' inner rect) live in VECTOR registers.
+    // As kernel arguments they are scalar values, loaded eight dwords at a time together with the reward multipliers, and the loop has
+    // no scalar registers left for them: the allocator parks them in lanes of a VGPR and every use in the loop reads the whole group
+    // back (v_readlane + hazard slots: 48 of the 114 lane reads in the loop's head run, tools/loop_spill_traffic.py).  Only where
+    // vector registers are to spare: the single-step kernels with fp64 arithmetic (G 241 of 256, no spills in any of their rows).  The
+    // budgeted and the multi-step kernels sit at 256, and the all-fp32 rows are capped at 168 / 128 VGPRs by their launch bounds and
+    // already spill (five more pinned registers only added scratch traffic there): those keep the arguments as they are.
+    // Uniform values in vector registers: same operands, same operations, same results.
+    SimParams<typename C::Real> sph = sp;
+    if constexpr (!MULTI && !BUDGET && sizeof(typename C::Real) == 8) {
+        asm volatile("" : "+v"(sph.W), "+v"(sph.H), "+v"(sph.rob_cdist));
+        asm volatile("" : "+v"(sph.inner_h), "+v"(sph.inner_cdist));
+    }
     if constexpr (!MULTI) {
         StepOut<O> o = { obs, obs_g, reward, reward_g, done, status, sp.memo ? snap : nullptr, isnap, arena,
                          (int)Arena<C>::SNAP_WORDS, (int)Arena<C>::ISNAP_WORDS };
         if constexpr (BUDGET) {
             ParkCtx pk;
             pk.buf = park + (size_t)arena * Arena<C>::PARK_WORDS; pk.budget = budget; pk.t_begin = t_begin;
-            step_arena<C, O, true>(A, sp, sp.arena_offset + (uint64_t)arena, actions ? actions + (size_t)arena * na : nullptr,
+            step_arena<C, O, true>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (size_t)arena * na : nullptr,
                                    thrust ? thrust + (size_t)arena * 2 * na : nullptr, na, o, pk);
         } else {
-            step_arena<C, O>(A, sp, sp.arena_offset + (uint64_t)arena, actions ? actions + (size_t)arena * na : nullptr,
+            step_arena<C, O>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (size_t)arena * na : nullptr,
                              thrust ? thrust + (size_t)arena * 2 * na : nullptr, na, o);
         }
     } else {
@@ -107,7 +120,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
                              status ? status + so : nullptr, sp.memo ? snap : nullptr, isnap, arena,
                              (int)Arena<C>::SNAP_WORDS, (int)Arena<C>::ISNAP_WORDS };
             const size_t ao = repeat ? 0 : so;
-            step_arena<C, O>(A, sp, sp.arena_offset + (uint64_t)arena, actions ? actions + (ao + (size_t)arena) * na : nullptr,
+            step_arena<C, O>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (ao + (size_t)arena) * na : nullptr,
                              thrust ? thrust + (ao + (size_t)arena) * 2 * na : nullptr, na, o);
         }
     }

@@ -174,32 +174,35 @@ class RRError(RuntimeError):
 
 def check(rc, what, lib=None, err_fn="rr_last_error"):
     """Raises RRError with the message of the library that returned `rc` (`lib`; the env passes its own -- the default and the
-    parity library keep separate thread-local strings).  `err_fn`: the entry point that holds the message -- the rr_dqn_* calls
-    write theirs to rr_dqn_last_error."""
+    parity library keep separate thread-local strings).  `err_fn`: the entry point that holds the message."""
     if rc != 0:
         libs = [lib] if lib is not None else [x for x in (_lib, _lib_exact) if x is not None] or [load()]
         msg = b"; ".join(m for m in (getattr(x, err_fn)() for x in libs) if m)
         raise RRError(f"{what} failed ({rc}): {msg.decode() if msg else '?'}")
 
 
-def check_dqn(rc, what, lib):
-    check(rc, what, lib, "rr_dqn_last_error")
+def ptr(t, offset=0):
+    """a tensor's (or None's) device pointer as the C-ABI takes it, `offset` bytes in: c_void_p, or None"""
+    return C.c_void_p(t.data_ptr() + offset) if t is not None else None
 
 
-class DqnHandle:
-    """Owner of one rr_dqn handle (rr_dqn_create .. rr_dqn_destroy): the per-workgroup partial gradients and the Adam moments of the fused
-    learn step, ~73 MB of device memory.  `h` is the handle (None once closed), `lib` the library it lives in."""
+def current_stream(device):
+    """the device's current torch stream, as the C-ABI takes it"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
-    def __init__(self, device):
-        self.device, self.lib, self.h = device, load(), None
-        h = C.c_void_p()
-        check_dqn(self.lib.rr_dqn_create(device.index or 0, C.byref(h)), "rr_dqn_create", self.lib)
-        self.h = h
+
+class _Handle:
+    """Owner of one C-ABI handle: `lib` the library it lives in, `h` the handle (None once closed), `device` the torch device its launches
+    go to.  A subclass names the entry that destroys the handle and the one that holds its library's error message."""
+    DESTROY = ERR = None
+
+    def __init__(self, lib, h, device):
+        self.lib, self.h, self.device = lib, h, device
 
     def close(self):
         h, self.h = getattr(self, "h", None), None
         if h:
-            self.lib.rr_dqn_destroy(h)
+            getattr(self.lib, self.DESTROY)(h)
 
     def __del__(self):
         try:
@@ -209,16 +212,46 @@ class DqnHandle:
 
     def stream(self):
         """the device's current torch stream, as the C-ABI takes it"""
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return current_stream(self.device)
 
     def call(self, name, *args):
-        """lib.<name>(handle, *args), an RRError with rr_dqn_last_error's message unless it returns 0"""
-        check_dqn(getattr(self.lib, name)(self.h, *args), name, self.lib)
+        """lib.<name>(handle, *args); an RRError that names <name> and carries the library's message unless it returns 0"""
+        rc = getattr(self.lib, name)(self.h, *args)
+        if rc:
+            check(rc, name, self.lib, self.ERR)
+
+    def launch(self, name, *args):
+        """call() with the device's current stream appended: the entries that enqueue work take it last"""
+        rc = getattr(self.lib, name)(self.h, *args, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc:
+            check(rc, name, self.lib, self.ERR)
+
+
+class EnvHandle(_Handle):
+    """Owner of one env handle (rr_create .. rr_destroy): the arenas' records on the device.  EnvHandle(lib, h, device) adopts a handle
+    that exists; create() makes one."""
+    DESTROY, ERR = "rr_destroy", "rr_last_error"
+
+    @classmethod
+    def create(cls, lib, cfg, device):
+        h = C.c_void_p()
+        check(lib.rr_create(C.byref(cfg), C.byref(h)), "rr_create", lib)
+        return cls(lib, h, device)
+
+
+class DqnHandle(_Handle):
+    """Owner of one rr_dqn handle (rr_dqn_create .. rr_dqn_destroy): the per-workgroup partial gradients and the Adam moments of the fused
+    learn step, ~73 MB of device memory.  The rr_dqn_* calls write their messages to rr_dqn_last_error."""
+    DESTROY, ERR = "rr_dqn_destroy", "rr_dqn_last_error"
+
+    def __init__(self, device):
+        lib, h = load(), C.c_void_p()
+        check(lib.rr_dqn_create(device.index or 0, C.byref(h)), "rr_dqn_create", lib, self.ERR)
+        super().__init__(lib, h, device)
 
     def act(self, params, obs, n, epsilon, seed, calls, actions, q=None, stream=None):
         """rr_dqn_act on the 11-256-256-8 network `params` (its six tensors): epsilon-greedy int32 actions for the n rows of `obs`, the
         draws keyed by (seed, row, the low 32 bits of `calls`); q: optionally the float32 [n, 8] Q-values it acted on."""
         ptrs = (C.c_void_p * 6)(*[p.data_ptr() for p in params])
-        self.call("rr_dqn_act", C.byref(ptrs), C.c_void_p(obs.data_ptr()), n, float(min(max(epsilon, 0.0), 1.0)), int(seed),
-                  calls & 0xFFFFFFFF, C.c_void_p(actions.data_ptr()), C.c_void_p(q.data_ptr()) if q is not None else None,
-                  self.stream() if stream is None else stream)
+        self.call("rr_dqn_act", C.byref(ptrs), ptr(obs), n, float(min(max(epsilon, 0.0), 1.0)), int(seed), calls & 0xFFFFFFFF, ptr(actions),
+                  ptr(q), self.stream() if stream is None else stream)

@@ -288,10 +288,9 @@ class BatchedDQNAgent(_ReplayAgent):
         v = valid.to(torch.bool).contiguous() if valid is not None else None
         if not hasattr(self, "_store_count"):
             self._store_count = torch.zeros(1, dtype=torch.int32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        self._dqn.call("rr_dqn_store", p(s), p(a), p(r), p(s2), p(d), p(v), n, self.mem_cntr, self.mem_size, p(self.state_memory),
-                       p(self.new_state_memory), p(self.action_memory), p(self.reward_memory), p(self.terminal_memory), p(self._store_count),
-                       self._dqn.stream())
+        p = _lib.ptr
+        self._dqn.launch("rr_dqn_store", p(s), p(a), p(r), p(s2), p(d), p(v), n, self.mem_cntr, self.mem_size, p(self.state_memory),
+                         p(self.new_state_memory), p(self.action_memory), p(self.reward_memory), p(self.terminal_memory), p(self._store_count))
         self.mem_cntr += n if v is None else int(self._store_count.item())  # (the one host read of the call, as in the PyTorch path)
 
     def _act_fused(self, observation, eps):
@@ -320,7 +319,7 @@ class BatchedDQNAgent(_ReplayAgent):
     def _learn_fused(self, max_mem):
         """sampling in PyTorch (one or two kernels), everything else in rr_dqn_update's two launches"""
         batch = self._sample(max_mem).contiguous()
-        self._dqn.call("rr_dqn_update", C.byref(self._fused_args(batch)), self._dqn.stream())
+        self._dqn.launch("rr_dqn_update", C.byref(self._fused_args(batch)))
         self._keep = batch  # the launch reads it asynchronously
         return self._fused_loss[0]
 
@@ -329,7 +328,7 @@ class BatchedDQNAgent(_ReplayAgent):
         n = self._rrlib.rr_dqn_param_count()
         flat = torch.empty(n, device=self.device)
         args = self._fused_args(batch.contiguous())
-        self._dqn.call("rr_dqn_grads", C.byref(args), C.c_void_p(flat.data_ptr()), self._dqn.stream())
+        self._dqn.launch("rr_dqn_grads", C.byref(args), _lib.ptr(flat))
         torch.cuda.current_stream(self.device).synchronize()
         names = ["fc2.weight", "fc1.weight", "fc3.weight", "fc1.bias", "fc2.bias", "fc3.bias"]  # the handle's flat order
         shapes = dict(self.Q_eval.named_parameters())
@@ -397,8 +396,7 @@ class BatchedDQNAgent(_ReplayAgent):
         else:
             m1, m2 = state["exp_avg"].to(self.device).contiguous(), state["exp_avg_sq"].to(self.device).contiguous()
             step = C.c_int64(int(state["step"]))
-        self._dqn.call("rr_dqn_adam_state", C.c_void_p(m1.data_ptr()), C.c_void_p(m2.data_ptr()), C.byref(step), 0 if state is None else 1,
-                       self._dqn.stream())
+        self._dqn.launch("rr_dqn_adam_state", _lib.ptr(m1), _lib.ptr(m2), C.byref(step), 0 if state is None else 1)
         torch.cuda.current_stream(self.device).synchronize()
         return dict(exp_avg=m1, exp_avg_sq=m2, step=step.value)
 
@@ -555,9 +553,8 @@ class PixelDQNAgent(_ReplayAgent):
             assert qvalues.dtype == torch.float32 and qvalues.is_contiguous() and tuple(qvalues.shape) == (n, 8)
         ptrs = (C.c_void_p * 8)(*[p.data_ptr() for p in params])
         self._act_calls += 1
-        self._dqn.call("rr_cnn_act", C.byref(ptrs), C.c_void_p(pixels.data_ptr()), n, self.channels, float(min(max(eps, 0.0), 1.0)),
-                       int(self._seed), self._act_calls & 0xFFFFFFFF, C.c_void_p(out.data_ptr()),
-                       C.c_void_p(qvalues.data_ptr()) if qvalues is not None else None, self._dqn.stream())
+        self._dqn.launch("rr_cnn_act", C.byref(ptrs), _lib.ptr(pixels), n, self.channels, float(min(max(eps, 0.0), 1.0)), int(self._seed),
+                         self._act_calls & 0xFFFFFFFF, _lib.ptr(out), _lib.ptr(qvalues))
         return out
 
     @torch.no_grad()

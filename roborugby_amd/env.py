@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr
 from .config import PRESETS, ENV_IDS, Preset
 from .spaces import Box, Discrete
 
@@ -73,8 +74,15 @@ class DebugInfo(dict):
         self.status = status
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+def _expect(what, t, dtypes, numel, at_least=False, device=None):
+    """The contract of a tensor handed to a launch -- contiguous, one of `dtypes`, exactly (at_least: at least) `numel` elements, on
+    `device` when one is named -- as an AssertionError"""
+    assert t.dtype in dtypes and t.is_contiguous() and (t.numel() >= numel if at_least else t.numel() == numel) \
+        and (device is None or t.device == device), f"{what}: a contiguous {' / '.join(str(d) for d in dtypes)} tensor of " \
+        f"{'at least ' if at_least else ''}{numel} elements{'' if device is None else f' on {device}'}"
+
+
+_I32, _U8 = (torch.int32,), (torch.uint8, torch.bool)
 
 
 # rr_config.dtype (include/roborugby_amd.h): "f64" = the reference's arithmetic, state and arithmetic in fp64 (parity mode, default);
@@ -139,11 +147,11 @@ class BatchedRoboRugbyEnv:
         counts = (p.nr_happy, p.nr_grumpy, p.nb_pos, p.nb_neg)
         from . import build as _build
         if counts in _build.BUILT_SHAPES:
-            self._lib = _lib.load(exact=self.exact_trig)
+            lib = _lib.load(exact=self.exact_trig)
         else:  # the reference's entity counts are free integers (RR_Constants.py:30-34): a library for this one shape, compiled on demand
             if dtype == "f32":
                 raise ValueError("entity counts outside the built shapes: dtype 'f64' or 'f32_state'")
-            self._lib = _lib.load_shape(counts, exact=self.exact_trig)
+            lib = _lib.load_shape(counts, exact=self.exact_trig)
         cfg = _lib.RRConfig(
             struct_size=C.sizeof(_lib.RRConfig), num_envs=self.num_envs, nr_happy=p.nr_happy, nr_grumpy=p.nr_grumpy,
             nb_pos=p.nb_pos, nb_neg=p.nb_neg, arena_w=p.arena_w, arena_h=p.arena_h, game_len_steps=p.game_len_steps,
@@ -153,9 +161,7 @@ class BatchedRoboRugbyEnv:
             arena_offset=int(arena_offset), step_budget_clocks=int(step_budget_clocks), reserved_=0)
         self.step_budget_clocks = int(step_budget_clocks)
         self._bout = None  # persistent step outputs of the budgeted mode (NOT_READY rows keep their previous observation)
-        h = C.c_void_p()
-        _lib.check(self._lib.rr_create(C.byref(cfg), C.byref(h)), "rr_create", self._lib)
-        self._h = h
+        self._handle = _lib.EnvHandle.create(lib, cfg, self.device)
         # other mixin stacks of the reference: `rewards` in class order like the reference's env classes
         # (RR_Environments.py), `observer` one of OBSERVERS.  SimpleDuel3's own stack is the default and stays fused in
         # the step kernel; anything else runs in light side kernels around it.
@@ -164,18 +170,17 @@ class BatchedRoboRugbyEnv:
         self.observer, self.obs_kind = observer, OBSERVERS[observer]
         self.obs_dim = observer_dim(self.obs_kind, p.nr, p.nb)
         if self.obs_kind == 4:  # the prior-step copies have to be snapshotted at every on_step_begin from now on
-            _lib.check(self._lib.rr_track_prior_step(self._h, 1, self._stream()), "rr_track_prior_step", self._lib)
+            self.track_prior_step()
         self.rewards = tuple(rewards)
         prog = np.asarray(keeper_exec_order(self.rewards), np.int32)
-        _lib.check(self._lib.rr_set_reward_program(self._h, prog.ctypes.data_as(C.c_void_p), len(prog)),
-                   "rr_set_reward_program", self._lib)
+        self._handle.call("rr_set_reward_program", prog.ctypes.data_as(C.c_void_p), len(prog))
         # Opt-in goal scoring -- an EXTENSION: the reference's goals never score on its live path
         # (RR_Goal.py:58-91 is only reached from the never-called __old_step and is broken), so this has no reference behaviour
         # to match.  A ball inside a goal triangle for 150 consecutive steps is consumed (out of play), +-500 points, three
         # negative balls destroy a goal, a destroyed goal / an empty field ends the episode (include/roborugby_amd.h).
         self.goal_scoring = bool(goal_scoring)
         if self.goal_scoring:
-            _lib.check(self._lib.rr_set_goal_scoring(self._h, 1, self._stream()), "rr_set_goal_scoring", self._lib)
+            self._handle.launch("rr_set_goal_scoring", 1)
         m = max(p.arena_w, p.arena_h, 360)  # RR_Observers.py:30-37
         self.observation_space = Box(-m, m, (self.obs_dim,), np.float32)
         # GameEnv_Simple: Discrete(8) (RR_EnvBase.py:610); bare GameEnv: Box(-1, 1, (2*happy robots,)) (RR_EnvBase.py:118-123),
@@ -215,11 +220,35 @@ class BatchedRoboRugbyEnv:
     def unwrapped(self):
         return self
 
+    # the C-ABI's handle, its library and the current stream, as tests and tools hand them to raw calls
+    _h = property(lambda self: self._handle.h)
+    _lib = property(lambda self: self._handle.lib)
+
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return self._handle.stream()
 
     def _new(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
+
+    def _step_outputs(self, lead, fd=torch.float32, alloc=torch.empty):
+        """(obs, reward, done_u8, obs_g, reward_g, status) of a step: leading shape `lead` -- (N,), a rollout's (S, N) --, float dtype fd"""
+        def new(*tail, dtype=fd):
+            return alloc(lead + tail, dtype=dtype, device=self.device)
+        return new(11), new(), new(dtype=torch.uint8), new(11) if self.has_grumpy else None, new(), new(dtype=torch.int32)
+
+    def _step_result(self, obs, rew, done, obs_g, rew_g, status, observe=True):
+        """what a step returns from its six outputs; observe: under another observer than the fused one, that observer's view"""
+        if observe and self.obs_kind != 0:
+            obs, obs_g = self.get_game_state(1), (self.get_game_state(-1) if self.has_grumpy else None)
+        return obs, rew, done.view(torch.bool), DebugInfo(obs_g, rew_g, status)
+
+    def _set(self, name, *tensors, reseed=True):
+        """The tail of a setter: the launch, a wait for it (the inputs may be temporaries) and -- reseed: set_state and set_poses, which
+        rewrite the poses the observations are made of -- on a handle that has had a budget the persistent step outputs seeded again"""
+        self._handle.launch(name, *map(ptr, tensors))
+        torch.cuda.current_stream(self.device).synchronize()
+        if reseed and self._bout is not None:
+            self._seed_bout()
 
     def _seed_bout(self, mask=None, obs=None):
         """Budgeted mode: the persistent step outputs, with both teams' observation rows of the arenas in `mask` (None: all) set to
@@ -229,10 +258,7 @@ class BatchedRoboRugbyEnv:
         `obs`); the other rows keep what step() handed out: a parked arena's record holds the middle of its step, not an observation."""
         N = self.num_envs
         if self._bout is None:
-            self._bout = (self._new((N, 11), torch.float32), torch.zeros(N, dtype=torch.float32, device=self.device),
-                          torch.zeros(N, dtype=torch.uint8, device=self.device),
-                          self._new((N, 11), torch.float32) if self.has_grumpy else None,
-                          torch.zeros(N, dtype=torch.float32, device=self.device), torch.zeros(N, dtype=torch.int32, device=self.device))
+            self._bout = self._step_outputs((N,), alloc=torch.zeros)  # (reward, done and status read 0 until a step writes them)
             mask = None
         for team, rows in ((1, self._bout[0]), (-1, self._bout[3])):
             if rows is None:
@@ -241,7 +267,7 @@ class BatchedRoboRugbyEnv:
                 cur = obs
             else:
                 cur = rows if mask is None else self._new((N, 11), torch.float32)
-                _lib.check(self._lib.rr_observe(self._h, team, -1, -1, _ptr(cur), self._stream()), "rr_observe", self._lib)
+                self._handle.launch("rr_observe", team, -1, -1, ptr(cur))
             if mask is not None:
                 rows.copy_(torch.where(mask.view(N, 1).bool(), cur, rows))
             elif cur is not rows:
@@ -249,8 +275,7 @@ class BatchedRoboRugbyEnv:
 
     # ---------------------------------------------------------------- gym surface
     def _reset_to_start(self, mask, obs):
-        _lib.check(self._lib.rr_reset_to_poses(self._h, _ptr(mask), _ptr(self._start_robots), _ptr(self._start_balls), _ptr(obs),
-                                               None, self._stream()), "rr_reset_to_poses", self._lib)
+        self._handle.launch("rr_reset_to_poses", ptr(mask), ptr(self._start_robots), ptr(self._start_balls), ptr(obs), None)
 
     def _mask(self, mask):
         """uint8 [N] device mask; scalars / wrong sizes are rejected (the kernels index mask[arena] for every arena)."""
@@ -276,12 +301,12 @@ class BatchedRoboRugbyEnv:
         mask = self._mask(mask)
         if mask is not None:
             # rows that are not reset keep their current observation; a parked arena has none (its record is mid-step)
-            _lib.check(self._lib.rr_observe(self._h, 1, -1, -1, _ptr(obs), self._stream()), "rr_observe", self._lib)
+            self._handle.launch("rr_observe", 1, -1, -1, ptr(obs))
             if self._bout is not None:
                 parked = (self._bout[5] & STATUS_NOT_READY) != 0
                 obs = torch.where(parked.view(N, 1), self._bout[0], obs).contiguous()
         if bln_randomize_pos:
-            _lib.check(self._lib.rr_reset(self._h, _ptr(mask), _ptr(obs), None, self._stream()), "rr_reset", self._lib)
+            self._handle.launch("rr_reset", ptr(mask), ptr(obs), None)
         else:
             self._reset_to_start(mask, obs)
         if self._bout is not None:  # budgeted mode: a NOT_READY row of the next step keeps these observations
@@ -307,34 +332,30 @@ class BatchedRoboRugbyEnv:
             raise ValueError(f"actions must be [N] or [N,NA]; got {tuple(a.shape)}")
         if a.shape[1] > self.preset.nr:  # RR_EnvBase.py:621-622
             raise Exception(f"{a.shape[1]} commands but only {self.preset.nr} robots.")
-        a = a.to(torch.int32).contiguous()
         own = out is None and (bool(self.step_budget_clocks) or self._bout is not None)  # (budget 0 after a budget: parks may remain)
         if own:
             if self._bout is None:  # rows of parked arenas are not written: they must find their previous observation here
                 self._seed_bout()
             out = self._bout
-        if out is None:
-            obs, rew = self._new((N, 11), torch.float32), self._new((N,), torch.float32)
-            done = self._new((N,), torch.uint8)
-            obs_g = self._new((N, 11), torch.float32) if self.has_grumpy else None
-            rew_g = self._new((N,), torch.float32)
-            status = self._new((N,), torch.int32)
-        else:
-            obs, rew, done, obs_g, rew_g, status = out
-        _lib.check(self._lib.rr_step(self._h, _ptr(a), a.shape[1], _ptr(obs), _ptr(rew), _ptr(done), _ptr(obs_g),
-                                     _ptr(rew_g), _ptr(status), self._stream()), "rr_step", self._lib)
+        out = self._step_discrete("rr_step", a, out)
         if own:  # hand out copies: the persistent buffers are overwritten by the next call
-            obs, rew, done, rew_g, status = obs.clone(), rew.clone(), done.clone(), rew_g.clone(), status.clone()
-            obs_g = obs_g.clone() if obs_g is not None else None
-        if self.obs_kind != 0:
-            obs, obs_g = self.get_game_state(1), (self.get_game_state(-1) if self.has_grumpy else None)
-        return obs, rew, done.view(torch.bool), DebugInfo(obs_g, rew_g, status)
+            out = [t.clone() if t is not None else None for t in out]
+        return self._step_result(*out)
+
+    def _step_discrete(self, name, a, out=None, fd=torch.float32):
+        """What step and step_f64 share: rr_step / rr_step_f64 on the actions a [N, NA] into `out`, or into fresh outputs of float
+        dtype fd -> the six outputs"""
+        a = a.to(torch.int32).contiguous()
+        if out is None:
+            out = self._step_outputs((self.num_envs,), fd)
+        self._handle.launch(name, ptr(a), a.shape[1], *map(ptr, out))
+        return out
 
     def set_step_budget(self, clocks):
         """rr_set_step_budget: switch the budgeted step on (clocks > 0) or off (0: parked arenas finish in the next calls), or change
         the budget.  Arenas parked at the time go on with their step; the NOT_READY rows of step() keep their previous observation
         (once a handle has had a budget, step() without `out` hands out the persistent buffers whatever the budget)."""
-        _lib.check(self._lib.rr_set_step_budget(self._h, int(clocks)), "rr_set_step_budget", self._lib)
+        self._handle.call("rr_set_step_budget", int(clocks))
         self.step_budget_clocks = int(clocks)
         if self.step_budget_clocks and self._bout is None:
             self._seed_bout()
@@ -359,13 +380,9 @@ class BatchedRoboRugbyEnv:
         if a.shape[-2] != N or self.action_mode != "discrete" or self.obs_kind != 0:
             raise ValueError("rollout: discrete actions [S,N(,NA)] and the default observer only")
         if out is None:
-            out = (self._new((S, N, 11), torch.float32), self._new((S, N), torch.float32), self._new((S, N), torch.uint8),
-                   self._new((S, N, 11), torch.float32) if self.has_grumpy else None, self._new((S, N), torch.float32),
-                   self._new((S, N), torch.int32))
-        obs, rew, done, obs_g, rew_g, status = out
-        _lib.check(self._lib.rr_rollout(self._h, _ptr(a), na, S, rep, _ptr(obs), _ptr(rew), _ptr(done), _ptr(obs_g), _ptr(rew_g),
-                                        _ptr(status), self._stream()), "rr_rollout", self._lib)
-        return obs, rew, done.view(torch.bool), DebugInfo(obs_g, rew_g, status)
+            out = self._step_outputs((S, N))
+        self._handle.launch("rr_rollout", ptr(a), na, S, rep, *map(ptr, out))
+        return self._step_result(*out)
 
     def step_thrust(self, thrust, f64=False):
         """GameEnv.step with continuous (L,R) thrust pairs (RR_EnvBase.py:260-273): float tensor [N, 2*k].  f64=True returns the
@@ -374,30 +391,16 @@ class BatchedRoboRugbyEnv:
         t = torch.as_tensor(thrust, device=self.device, dtype=torch.float32).contiguous().view(N, -1)
         if t.shape[1] % 2 or t.shape[1] > 2 * self.preset.nr:  # RR_EnvBase.py:270-271
             raise Exception(f"{t.shape[1]} commands but only {self.preset.nr * 2} robot engines.")
-        od = torch.float64 if f64 else torch.float32
-        obs, rew = self._new((N, 11), od), self._new((N,), od)
-        done = self._new((N,), torch.uint8)
-        obs_g = self._new((N, 11), od) if self.has_grumpy else None
-        rew_g, status = self._new((N,), od), self._new((N,), torch.int32)
-        fn = self._lib.rr_step_thrust_f64 if f64 else self._lib.rr_step_thrust
-        _lib.check(fn(self._h, _ptr(t), t.shape[1] // 2, _ptr(obs), _ptr(rew), _ptr(done),
-                      _ptr(obs_g), _ptr(rew_g), _ptr(status), self._stream()), "rr_step_thrust", self._lib)
-        if self.obs_kind != 0:
-            obs, obs_g = self.get_game_state(1), (self.get_game_state(-1) if self.has_grumpy else None)
-        return obs, rew, done.view(torch.bool), DebugInfo(obs_g, rew_g, status)
+        out = self._step_outputs((N,), torch.float64 if f64 else torch.float32)
+        self._handle.launch("rr_step_thrust_f64" if f64 else "rr_step_thrust", ptr(t), t.shape[1] // 2, *map(ptr, out))
+        return self._step_result(*out)
 
     def step_f64(self, actions):
         """Same step with fp64 outputs (parity checks against the fp64 reference arithmetic)."""
         N = self.num_envs
         a = torch.as_tensor(actions, device=self.device)
-        a = (a.view(N, 1) if a.dim() == 1 else a).to(torch.int32).contiguous()
-        obs, rew = self._new((N, 11), torch.float64), self._new((N,), torch.float64)
-        done = self._new((N,), torch.uint8)
-        obs_g = self._new((N, 11), torch.float64) if self.has_grumpy else None
-        rew_g, status = self._new((N,), torch.float64), self._new((N,), torch.int32)
-        _lib.check(self._lib.rr_step_f64(self._h, _ptr(a), a.shape[1], _ptr(obs), _ptr(rew), _ptr(done), _ptr(obs_g),
-                                         _ptr(rew_g), _ptr(status), self._stream()), "rr_step_f64", self._lib)
-        return obs, rew, done.view(torch.bool), DebugInfo(obs_g, rew_g, status)
+        out = self._step_discrete("rr_step_f64", a.view(N, 1) if a.dim() == 1 else a, fd=torch.float64)
+        return self._step_result(*out, observe=False)  # (the fused observer's, whatever the env's own)
 
     def get_game_state(self, int_team=None, robot_idx=-1, ball_idx=-1, f64=False, observer=None):
         """get_game_state of the configured (or named) observer mixin (RR_Observers.py); None when the reference
@@ -408,8 +411,7 @@ class BatchedRoboRugbyEnv:
             return None
         dim = observer_dim(kind, self.preset.nr, self.preset.nb)
         obs = self._new((self.num_envs, dim), torch.float64 if f64 else torch.float32)
-        fn = self._lib.rr_observe_kind_f64 if f64 else self._lib.rr_observe_kind
-        _lib.check(fn(self._h, kind, team, int(robot_idx), int(ball_idx), _ptr(obs), dim, self._stream()), "rr_observe_kind", self._lib)
+        self._handle.launch("rr_observe_kind_f64" if f64 else "rr_observe_kind", kind, team, int(robot_idx), int(ball_idx), ptr(obs), dim)
         return obs
 
     @property
@@ -427,52 +429,49 @@ class BatchedRoboRugbyEnv:
         held=True (rr_hive_observe_held, the budgeted step): -> (assign, obs, held uint8 [N]); the rows of an arena parked mid-step are
         NOT written -- they stay what `out` holds, the rows of the step it is in the middle of -- and held is 1 there; out: (assign, obs,
         held) to reuse (without `out` the rows of held arenas are 0 / -1)."""
-        p, N = self.preset, self.num_envs
-        mask = (1 << p.nr_happy) - 1 if robot_mask is None else int(robot_mask)
-        kind = (self.obs_kind if self.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
-        od = torch.float64 if f64 else torch.float32
+        N, nr = self.num_envs, self.preset.nr
+        mask, kind, od = self._hive_args(robot_mask, observer, f64)
         if out is None and held:
-            out = (torch.full((N, p.nr), -1, dtype=torch.int32, device=self.device), torch.zeros((N, p.nr, 11), dtype=od, device=self.device),
+            out = (torch.full((N, nr), -1, dtype=torch.int32, device=self.device), torch.zeros((N, nr, 11), dtype=od, device=self.device),
                    self._new((N,), torch.uint8))
         elif out is None:
-            out = (self._new((N, p.nr), torch.int32), self._new((N, p.nr, 11), od))
-        assign, obs = out[:2]
-        assert assign.dtype == torch.int32 and assign.is_contiguous() and assign.numel() == N * p.nr
-        assert obs.dtype == od and obs.is_contiguous() and obs.numel() >= N * p.nr * 11
+            out = (self._new((N, nr), torch.int32), self._new((N, nr, 11), od))
+        out = tuple(out[:3 if held else 2])
+        _expect("assign", out[0], _I32, N * nr)
+        _expect("obs", out[1], (od,), N * nr * 11, at_least=True)
+        if held:
+            _expect("held", out[2], _U8, N, device=self.device)
+        self._handle.launch("rr_hive_observe" + ("_held" if held else "") + ("_f64" if f64 else ""), mask, kind, *map(ptr, out))
+        return out
+
+    def _hive_args(self, robot_mask, observer, f64=False):
+        """What every hive entry starts with -> (mask, kind, float dtype).  robot_mask: one bit per robot, None = the happy team;
+        observer: None = the env's own when it is SingleBall_6wayLidar(_v2), else SingleBall_6wayLidar_v2; f64: the outputs' dtype"""
+        mask = (1 << self.preset.nr_happy) - 1 if robot_mask is None else int(robot_mask)
         if mask < 0 or mask > 0xFFFFFFFF:
             raise ValueError("robot_mask: one bit per robot")
-        if held:
-            hl = out[2]
-            assert hl.dtype in (torch.uint8, torch.bool) and hl.is_contiguous() and hl.numel() == N and hl.device == self.device
-            fn = self._lib.rr_hive_observe_held_f64 if f64 else self._lib.rr_hive_observe_held
-            _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(obs), _ptr(hl), self._stream()), "rr_hive_observe_held", self._lib)
-            return assign, obs, hl
-        fn = self._lib.rr_hive_observe_f64 if f64 else self._lib.rr_hive_observe
-        _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(obs), self._stream()), "rr_hive_observe", self._lib)
-        return assign, obs
+        kind = (self.obs_kind if self.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
+        return mask, kind, torch.float64 if f64 else torch.float32
 
     def hive_commit(self, fresh, assign, held, accepted, thrust, robot_mask=None):
         """The tail of the hive's turn under the budgeted step, in one launch (rr_hive_commit): for every arena that is not held and every
         robot of the mask, accepted[a, r] = fresh[a, r] and thrust[a, 2r:2r+2] = the (L, R) pair of that direction -- (0, 0) without a ball
         (assign < 0) or for a value outside 0..7.  Held arenas and robots outside the mask keep what `accepted` and `thrust` hold.
         fresh, assign, accepted: int32 [N,NR]; held: uint8 [N] (hive_observe(held=True)); thrust: float32 [N,2*NR].  -> (accepted, thrust)"""
-        p, N = self.preset, self.num_envs
-        mask = (1 << p.nr_happy) - 1 if robot_mask is None else int(robot_mask)
-        for t in (fresh, assign, accepted):
-            assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= N * p.nr and t.device == self.device
-        assert held.dtype in (torch.uint8, torch.bool) and held.is_contiguous() and held.numel() == N and held.device == self.device
-        assert thrust.dtype == torch.float32 and thrust.is_contiguous() and thrust.numel() == N * 2 * p.nr and thrust.device == self.device
-        if mask < 0 or mask > 0xFFFFFFFF:
-            raise ValueError("robot_mask: one bit per robot")
-        _lib.check(self._lib.rr_hive_commit(self._h, mask, _ptr(fresh), _ptr(assign), _ptr(held), _ptr(accepted), _ptr(thrust), self._stream()),
-                   "rr_hive_commit", self._lib)
+        N, nr, dev = self.num_envs, self.preset.nr, self.device
+        mask = self._hive_args(robot_mask, None)[0]
+        for what, t in (("fresh", fresh), ("assign", assign), ("accepted", accepted)):
+            _expect(what, t, _I32, N * nr, at_least=True, device=dev)
+        _expect("held", held, _U8, N, device=dev)
+        _expect("thrust", thrust, (torch.float32,), N * 2 * nr, device=dev)
+        self._handle.launch("rr_hive_commit", mask, ptr(fresh), ptr(assign), ptr(held), ptr(accepted), ptr(thrust))
         return accepted, thrust
 
     def track_prior_step(self, on=True):
         """rr_track_prior_step: every step from now on first snapshots what the sprites' on_step_begin copies (robot and ball centres at
         the step's begin).  observer='AllCoords_WithPrior' switches it on by itself; hive_transition needs it on BEFORE the step it
         looks back on."""
-        _lib.check(self._lib.rr_track_prior_step(self._h, int(bool(on)), self._stream()), "rr_track_prior_step", self._lib)
+        self._handle.launch("rr_track_prior_step", int(bool(on)))
 
     def hive_transition(self, assign, status, done, robot_mask=None, observer=None, f64=False, out=None):
         """Training the hive in the full game: the transition of every hive robot over the step that was just taken, in one launch
@@ -492,25 +491,20 @@ class BatchedRoboRugbyEnv:
         return self._hive_transition("rr_hive_transition_held", assign, status, done, robot_mask, observer, f64, out)
 
     def _hive_transition(self, name, assign, status, done, robot_mask, observer, f64, out):
-        p, N = self.preset, self.num_envs
-        mask = (1 << p.nr_happy) - 1 if robot_mask is None else int(robot_mask)
-        kind = (self.obs_kind if self.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
-        od = torch.float64 if f64 else torch.float32
+        N, nr, dev = self.num_envs, self.preset.nr, self.device
+        mask, kind, od = self._hive_args(robot_mask, observer, f64)
         if out is None:
-            out = (self._new((N, p.nr, 11), od), self._new((N, p.nr), od), self._new((N, p.nr), torch.uint8), self._new((N, p.nr), torch.uint8))
+            out = (self._new((N, nr, 11), od), self._new((N, nr), od), self._new((N, nr), torch.uint8), self._new((N, nr), torch.uint8))
         next_obs, reward, terminal, valid = out
-        assert assign.dtype == torch.int32 and assign.is_contiguous() and assign.numel() == N * p.nr and assign.device == self.device
-        assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == N and status.device == self.device
         done = done.view(torch.uint8) if done.dtype == torch.bool else done
-        assert done.dtype == torch.uint8 and done.is_contiguous() and done.numel() == N and done.device == self.device
-        assert next_obs.dtype == od and next_obs.is_contiguous() and next_obs.numel() >= N * p.nr * 11
-        assert reward.dtype == od and reward.is_contiguous() and reward.numel() >= N * p.nr
-        assert all(t.dtype in (torch.uint8, torch.bool) and t.is_contiguous() and t.numel() >= N * p.nr for t in (terminal, valid))
-        if mask < 0 or mask > 0xFFFFFFFF:
-            raise ValueError("robot_mask: one bit per robot")
-        fn = getattr(self._lib, name + ("_f64" if f64 else ""))
-        _lib.check(fn(self._h, mask, kind, _ptr(assign), _ptr(status), _ptr(done), _ptr(next_obs), _ptr(reward), _ptr(terminal), _ptr(valid),
-                      self._stream()), name, self._lib)
+        _expect("assign", assign, _I32, N * nr, device=dev)
+        _expect("status", status, _I32, N, device=dev)
+        _expect("done", done, (torch.uint8,), N, device=dev)
+        _expect("next_obs", next_obs, (od,), N * nr * 11, at_least=True)
+        _expect("reward", reward, (od,), N * nr, at_least=True)
+        _expect("terminal", terminal, _U8, N * nr, at_least=True)
+        _expect("valid", valid, _U8, N * nr, at_least=True)
+        self._handle.launch(name + ("_f64" if f64 else ""), mask, kind, ptr(assign), ptr(status), ptr(done), *map(ptr, out))
         return next_obs, reward, terminal, valid
 
     def render(self, mode="human", arena=0):
@@ -538,24 +532,32 @@ class BatchedRoboRugbyEnv:
         p = self.preset
         w = int(p.arena_w) if width is None else int(width)
         h = int(p.arena_h) if height is None else int(height)
-        idx = None
-        if arenas is not None:
-            idx = torch.as_tensor(arenas)
-            if idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 1:
-                raise ValueError("render_batch(arenas=...): a 1-D sequence of integer arena indices")
-            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        idx = None if arenas is None else self._index_list(arenas, "render_batch(arenas=...)")
         m = self.num_envs if idx is None else int(idx.numel())
+        out = self._frames("render_batch", m, w, h, (m, h, w, 3), out)
+        self._handle.launch("rr_render", ptr(idx), m, w, h, int(samples), ptr(out))
+        return out
+
+    def _index_list(self, x, where):
+        """int32 device tensor of a 1-D sequence of integer indices (render_batch / render_ego: arenas, robots)"""
+        x = torch.as_tensor(x)
+        if x.is_floating_point() or x.dtype == torch.bool or x.dim() != 1:
+            raise ValueError(f"{where}: a 1-D sequence of integer indices")
+        return x.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def _frames(self, method, m, w, h, shape, out):
+        """The m frames of w x h RGB pixels `method` (render_batch / render_ego) writes, as `shape`: `out` when it is given and fits,
+        else a new tensor; ValueError for no frame at all, for more than RENDER_BATCH_MAX_BYTES and for an `out` that does not fit"""
         if m < 1 or w < 1 or h < 1:
-            raise ValueError("render_batch: at least one frame of at least one pixel")
+            raise ValueError(f"{method}: at least one frame of at least one pixel")
         if m * h * w * 3 > self.RENDER_BATCH_MAX_BYTES:
-            raise ValueError(f"render_batch: {m} frames of {w}x{h} are {m * h * w * 3 / 2 ** 30:.2f} GiB, above the 1 GiB a call may write; "
-                             "render fewer arenas per call or smaller frames")
+            raise ValueError(f"{method}: {m} frames of {w}x{h} are {m * h * w * 3 / 2 ** 30:.2f} GiB, above the 1 GiB a call may write; "
+                             "render fewer frames per call or smaller ones")
         if out is None:
-            out = self._new((m, h, w, 3), torch.uint8)
-        elif not (out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == m * h * w * 3 and out.device == self.device):
-            raise ValueError(f"render_batch(out=...): a contiguous uint8 tensor of {m}x{h}x{w}x3 elements on {self.device}")
-        _lib.check(self._lib.rr_render(self._h, _ptr(idx), m, w, h, int(samples), _ptr(out), self._stream()), "rr_render", self._lib)
-        return out.view(m, h, w, 3)
+            return self._new(shape, torch.uint8)
+        if not (out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == m * h * w * 3 and out.device == self.device):
+            raise ValueError(f"{method}(out=...): a contiguous uint8 tensor of {m}x{h}x{w}x3 elements on {self.device}")
+        return out.view(shape)
 
     def render_ego(self, arenas=None, robots=None, width=64, height=None, span=400.0, ahead=0.0, samples=1, relative=True, planar=False,
                    out=None):
@@ -570,37 +572,20 @@ class BatchedRoboRugbyEnv:
         elements on the device to write into.  Raises ValueError before any launch when the result would exceed 1 GiB."""
         w = int(width)
         h = w if height is None else int(height)
-
-        def index_list(x, name):
-            x = torch.as_tensor(x)
-            if x.is_floating_point() or x.dtype == torch.bool or x.dim() != 1:
-                raise ValueError(f"render_ego({name}=...): a 1-D sequence of integer indices")
-            return x.to(device=self.device, dtype=torch.int32).contiguous()
-
-        idx = None if arenas is None else index_list(arenas, "arenas")
+        idx = None if arenas is None else self._index_list(arenas, "render_ego(arenas=...)")
         m = self.num_envs if idx is None else int(idx.numel())
         rob = None
         if robots is not None:
             if isinstance(robots, numbers.Integral) and not isinstance(robots, bool):
                 rob = torch.full((max(m, 1),), int(robots), dtype=torch.int32, device=self.device) if int(robots) != 0 else None
             else:
-                rob = index_list(robots, "robots")
+                rob = self._index_list(robots, "render_ego(robots=...)")
                 if int(rob.numel()) != m:
                     raise ValueError(f"render_ego(robots=...): {int(rob.numel())} robots for {m} frames")
-        if m < 1 or w < 1 or h < 1:
-            raise ValueError("render_ego: at least one frame of at least one pixel")
-        if m * h * w * 3 > self.RENDER_BATCH_MAX_BYTES:
-            raise ValueError(f"render_ego: {m} frames of {w}x{h} are {m * h * w * 3 / 2 ** 30:.2f} GiB, above the 1 GiB a call may write; "
-                             "render fewer frames per call or smaller ones")
-        shape = (m, 3, h, w) if planar else (m, h, w, 3)
-        if out is None:
-            out = self._new(shape, torch.uint8)
-        elif not (out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == m * h * w * 3 and out.device == self.device):
-            raise ValueError(f"render_ego(out=...): a contiguous uint8 tensor of {m}x{h}x{w}x3 elements on {self.device}")
+        out = self._frames("render_ego", m, w, h, (m, 3, h, w) if planar else (m, h, w, 3), out)
         flags = (1 if relative else 0) | (2 if planar else 0)  # RR_EGO_RELATIVE, RR_EGO_PLANAR
-        _lib.check(self._lib.rr_render_ego(self._h, _ptr(idx), _ptr(rob), m, w, h, int(samples), float(span), float(ahead), flags, _ptr(out),
-                                           self._stream()), "rr_render_ego", self._lib)
-        return out.view(shape)
+        self._handle.launch("rr_render_ego", ptr(idx), ptr(rob), m, w, h, int(samples), float(span), float(ahead), flags, ptr(out))
+        return out
 
     def seed(self, seed=None):
         """Like the reference (RR_EnvBase.py:568-570) this does not re-seed placement; the reset RNG is keyed at
@@ -608,15 +593,8 @@ class BatchedRoboRugbyEnv:
         return [seed]
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.rr_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if getattr(self, "_handle", None):  # (its own __del__ destroys a handle nobody closed)
+            self._handle.close()
 
     # ---------------------------------------------------------------- state exchange / logging
     def get_state(self):
@@ -626,20 +604,18 @@ class BatchedRoboRugbyEnv:
         robots_i = self._new((N, p.nr, 3), torch.int32)
         balls = self._new((N, p.nb, 8), torch.float64)
         step = self._new((N,), torch.int32)
-        _lib.check(self._lib.rr_get_state(self._h, _ptr(robots), _ptr(robots_i), _ptr(balls), _ptr(step), self._stream()),
-                   "rr_get_state", self._lib)
+        self._handle.launch("rr_get_state", ptr(robots), ptr(robots_i), ptr(balls), ptr(step))
         return dict(robots=robots, robots_i=robots_i, balls=balls, step=step)
 
     def set_scratch_rect(self, xy):
         """Parity build only (exact_trig=True): centre of the reference's module-global scratch rect, [N,2] fp64 -- e.g. the
         `state_inner[..., :2]` a golden trajectory dumped (include/roborugby_amd.h: rr_set_scratch_rect)."""
         xy = torch.as_tensor(xy, dtype=torch.float64, device=self.device).contiguous().view(self.num_envs, 2)
-        _lib.check(self._lib.rr_set_scratch_rect(self._h, _ptr(xy), self._stream()), "rr_set_scratch_rect", self._lib)
-        torch.cuda.current_stream(self.device).synchronize()
+        self._set("rr_set_scratch_rect", xy, reseed=False)
 
     def get_scratch_rect(self):
         xy = self._new((self.num_envs, 2), torch.float64)
-        _lib.check(self._lib.rr_get_scratch_rect(self._h, _ptr(xy), self._stream()), "rr_get_scratch_rect", self._lib)
+        self._handle.launch("rr_get_scratch_rect", ptr(xy))
         return xy
 
     def get_episode_state(self):
@@ -647,14 +623,13 @@ class BatchedRoboRugbyEnv:
         reset RNG: without it a resumed run would replay the placements of episodes 1, 2, ...), steps in the running
         episode, finished episodes, last episode's length, fault flag; `acc` [N,4] = running / last finished returns."""
         ints, acc = self._new((self.num_envs, 5), torch.int32), self._new((self.num_envs, 4), torch.float64)
-        _lib.check(self._lib.rr_get_episode_state(self._h, _ptr(ints), _ptr(acc), self._stream()), "rr_get_episode_state", self._lib)
+        self._handle.launch("rr_get_episode_state", ptr(ints), ptr(acc))
         return dict(ints=ints, acc=acc)
 
     def set_episode_state(self, ints, acc):
         ints = torch.as_tensor(ints, dtype=torch.int32, device=self.device).contiguous().view(self.num_envs, 5)
         acc = torch.as_tensor(acc, dtype=torch.float64, device=self.device).contiguous().view(self.num_envs, 4)
-        _lib.check(self._lib.rr_set_episode_state(self._h, _ptr(ints), _ptr(acc), self._stream()), "rr_set_episode_state", self._lib)
-        torch.cuda.current_stream(self.device).synchronize()
+        self._set("rr_set_episode_state", ints, acc, reseed=False)
 
     def checkpoint_state(self):
         """Everything a resumed run needs besides the agent: `env_state` (get_state), `episode` (get_episode_state: the episode index
@@ -680,28 +655,21 @@ class BatchedRoboRugbyEnv:
         robots_i = torch.as_tensor(robots_i, dtype=torch.int32, device=self.device).contiguous().view(N, p.nr, 3)
         balls = torch.as_tensor(balls, dtype=torch.float64, device=self.device).contiguous().view(N, p.nb, 8)
         step = torch.as_tensor(step, dtype=torch.int32, device=self.device).contiguous().view(N)
-        _lib.check(self._lib.rr_set_state(self._h, _ptr(robots), _ptr(robots_i), _ptr(balls), _ptr(step), self._stream()),
-                   "rr_set_state", self._lib)
-        torch.cuda.current_stream(self.device).synchronize()  # inputs may be temporaries
-        if self._bout is not None:
-            self._seed_bout()
+        self._set("rr_set_state", robots, robots_i, balls, step)
 
     def set_poses(self, robots_xyr, balls_xyv):
         """The reference's lst_starting_config (RR_EnvBase.py:35-52) per arena, plus ball velocities."""
         p, N = self.preset, self.num_envs
         r = torch.as_tensor(robots_xyr, dtype=torch.float64, device=self.device).contiguous().view(N, p.nr, 3)
         b = torch.as_tensor(balls_xyv, dtype=torch.float64, device=self.device).contiguous().view(N, p.nb, 4)
-        _lib.check(self._lib.rr_set_poses(self._h, _ptr(r), _ptr(b), self._stream()), "rr_set_poses", self._lib)
-        torch.cuda.current_stream(self.device).synchronize()
-        if self._bout is not None:
-            self._seed_bout()
+        self._set("rr_set_poses", r, b)
 
     def goal_scores(self):
         """Goal.get_score() of (happy, grumpy) goal (RR_Goal.py:87-88): identically 0 on the live path -- the reference
         never feeds its goal bookkeeping, so `done` is purely the step counter -- unless the env was
         built with goal_scoring=True (the opt-in extension): then 500 x (positive - negative balls the goal has consumed)."""
         s = self._new((self.num_envs, 2), torch.int32)
-        _lib.check(self._lib.rr_goal_scores(self._h, _ptr(s), self._stream()), "rr_goal_scores", self._lib)
+        self._handle.launch("rr_goal_scores", ptr(s))
         return s
 
     def episode_stats(self):
@@ -709,18 +677,17 @@ class BatchedRoboRugbyEnv:
         N = self.num_envs
         lr, lrg = self._new((N,), torch.float32), self._new((N,), torch.float32)
         ll, cnt = self._new((N,), torch.int32), self._new((N,), torch.int32)
-        _lib.check(self._lib.rr_episode_stats(self._h, _ptr(lr), _ptr(lrg), _ptr(ll), _ptr(cnt), self._stream()),
-                   "rr_episode_stats", self._lib)
+        self._handle.launch("rr_episode_stats", ptr(lr), ptr(lrg), ptr(ll), ptr(cnt))
         return lr, lrg, ll, cnt
 
     def lanes_per_env(self):
         v = C.c_int32()
-        _lib.check(self._lib.rr_lanes_per_env(self._h, C.byref(v)), "rr_lanes_per_env", self._lib)
+        self._handle.call("rr_lanes_per_env", C.byref(v))
         return v.value
 
     def state_bytes_per_env(self):
         b = C.c_int64()
-        _lib.check(self._lib.rr_state_bytes_per_env(self._h, C.byref(b)), "rr_state_bytes_per_env", self._lib)
+        self._handle.call("rr_state_bytes_per_env", C.byref(b))
         return b.value
 
 

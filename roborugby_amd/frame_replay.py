@@ -3,15 +3,10 @@ rr_frames_sample; csrc/rr_frames.hpp).  A dense replay of stacked observations h
 here a vector step adds ONE frame per row, and sampling rebuilds the two stacks of a transition from the at most stack + 1 distinct frames
 behind them.  Rows are arenas -- or (arena, robot) pairs of a PixelObservation with several robots --, slots are vector steps, so storing
 needs no compaction of the valid rows and nothing here synchronises with the host."""
-import ctypes as C
-
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from ._lib import ptr
 
 
 class FrameReplay:
@@ -86,9 +81,9 @@ class FrameReplay:
         f = None if (first is None or self._restart) else self._row_bytes(first, "first", torch.bool)
         a, r = self._row_bytes(action, "action", torch.int32), self._row_bytes(reward, "reward", torch.float32)
         d, v = self._row_bytes(done, "done", torch.bool), self._row_bytes(valid, "valid", torch.bool)
-        self._dqn.call("rr_frames_push", C.c_void_p(pixels.data_ptr() + stride - self.frame_bytes), stride, _p(f), _p(a), _p(r), _p(d), _p(v),
-                       self.rows, self.frame_bytes, self.slots, self.head, _p(self.frames), _p(self.age), _p(self.action), _p(self.reward),
-                       _p(self.flags), self._dqn.stream())
+        self._dqn.launch("rr_frames_push", ptr(pixels, stride - self.frame_bytes), stride, ptr(f), ptr(a), ptr(r), ptr(d), ptr(v),
+                         self.rows, self.frame_bytes, self.slots, self.head, ptr(self.frames), ptr(self.age), ptr(self.action), ptr(self.reward),
+                         ptr(self.flags))
         self._keep = (pixels, f, a, r, d, v)  # read asynchronously
         self.head += 1
         self._restart = False
@@ -115,8 +110,8 @@ class FrameReplay:
             if tuple(index.shape) != (batch, 2):
                 raise ValueError("FrameReplay.sample(index=...): int64 [batch, 2] of (push, row)")
         self.calls += 1
-        self._dqn.call("rr_frames_sample", _p(self.frames), _p(self.age), _p(self.action), _p(self.reward), _p(self.flags), self.rows,
-                       self.frame_bytes, self.slots, self.head, self.stack, batch, _p(index), self.seed & 0xFFFFFFFFFFFFFFFF,
-                       self.calls & 0xFFFFFFFF, _p(s), _p(s2), _p(a), _p(r), _p(t), _p(ok), None, self._dqn.stream())
+        self._dqn.launch("rr_frames_sample", ptr(self.frames), ptr(self.age), ptr(self.action), ptr(self.reward), ptr(self.flags), self.rows,
+                         self.frame_bytes, self.slots, self.head, self.stack, batch, ptr(index), self.seed & 0xFFFFFFFFFFFFFFFF,
+                         self.calls & 0xFFFFFFFF, ptr(s), ptr(s2), ptr(a), ptr(r), ptr(t), ptr(ok), None)
         self._keep_index = index
         return out

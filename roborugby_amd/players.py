@@ -3,9 +3,10 @@
 `Hive` is the reference's hive-mind player (DQN_pytorch_player.py: Stephen): one trained DQN policy drives every robot of the hive.
 `og_twitchy` is the reference's OG_Twitchy (robo_rugby/gym_env/RR_Players.py:14-30): per robot, 5 % turn left (-1, 1),
 45 % straight (1, 1), 45 % back (-1, -1), 5 % turn right (1, -1) -- as (L, R) thrust pairs for `step_thrust`."""
-import ctypes as C
-
 import torch
+
+from . import _lib
+from ._lib import ptr
 
 _TABLE = ((-1.0, 1.0), (1.0, 1.0), (-1.0, -1.0), (1.0, -1.0))
 
@@ -23,16 +24,12 @@ def chase(env, obs, step=0, noise=0.1, seed=0, na=None, step_of=None, out=None):
     ball (or drives forward within 8 degrees), `noise` of the arenas act at random, the other robots act at random.  ONE kernel
     launch on the current stream (rr_policy_chase); the draws are a function of (seed, global arena id, step index) -- `step`,
     or per arena `step_of` (int32 [N]).  Returns int32 [N, na]."""
-    from . import _lib
     na = env.preset.nr if na is None else int(na)
     if out is None:
         out = torch.empty(env.num_envs, na, dtype=torch.int32, device=env.device)
     obs = obs.contiguous()
     assert obs.dtype == torch.float32 and obs.shape == (env.num_envs, 11)
-    so = C.c_void_p(step_of.data_ptr()) if step_of is not None else None
-    _lib.check(env._lib.rr_policy_chase(env._h, C.c_void_p(obs.data_ptr()), so, int(step) & 0xFFFFFFFF, float(noise), int(seed),
-                                        C.c_void_p(out.data_ptr()), na, C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)),
-               "rr_policy_chase", env._lib)
+    env._handle.launch("rr_policy_chase", ptr(obs), ptr(step_of), int(step) & 0xFFFFFFFF, float(noise), int(seed), ptr(out), na)
     return out
 
 
@@ -58,15 +55,12 @@ class Hive:
     calls so far); a captured graph replays the draws of the call it captured."""
 
     def __init__(self, env, agent, robots=None, epsilon=0.2, seed=0, observer=None):
-        from . import _lib
-        from .env import OBSERVERS
         self.env, self.epsilon, self.seed = env, float(epsilon), int(seed)
         nr, N = env.preset.nr, env.num_envs
         self.robots = tuple(range(env.preset.nr_happy)) if robots is None else tuple(sorted({int(r) for r in robots}))
         if not self.robots or self.robots[0] < 0 or self.robots[-1] >= nr:
             raise ValueError(f"robots: a non-empty subset of 0..{nr - 1}")
-        self.mask = sum(1 << r for r in self.robots)
-        self.kind = (env.obs_kind if env.obs_kind in (0, 1) else 0) if observer is None else OBSERVERS[observer]
+        self.mask, self.kind, _ = env._hive_args(sum(1 << r for r in self.robots), observer)
         if self.kind not in (0, 1):
             raise ValueError("observer: 'SingleBall_6wayLidar_v2' or 'SingleBall_6wayLidar'")
         params = list(agent.Q_eval.parameters()) if hasattr(agent, "Q_eval") else list(agent)
@@ -147,7 +141,6 @@ class Hive:
         in `out` (0 in a fresh tensor), so another player -- `og_twitchy` -- can drive them.  status (optional, the last step's
         info.status): rows of arenas that are NOT_READY (budgeted step, parked mid-step) are left alone; the step ignores them.
         Without `status`, on an env that has (had) a step budget: the held pipeline (see the class)."""
-        from . import _lib
         env = self.env
         N, nr = env.num_envs, env.preset.nr
         if out is None:
@@ -156,8 +149,8 @@ class Hive:
         stream = self._dqn.stream()
         if status is None and env.has_had_budget:
             return self._act_held(out, stream)
-        _lib.check(env._lib.rr_hive_observe(env._h, self.mask, self.kind, C.c_void_p(self._assign.data_ptr()),
-                                            C.c_void_p(self._obs.data_ptr()), stream), "rr_hive_observe", env._lib)
+        # (the entry itself, not env.hive_observe: on the stream rr_dqn_act goes to, into buffers that are this object's own)
+        env._handle.call("rr_hive_observe", self.mask, self.kind, ptr(self._assign), ptr(self._obs), stream)
         self._dqn_act(self._actions, stream)
         torch.index_select(self._table, 0, self._actions[:N * nr], out=self._thrust)
         torch.ge(self._assign, 0, out=self._has)

@@ -463,6 +463,32 @@ int rr_dqn_adam_state(rr_dqn *dqn, float *exp_avg, float *exp_avg_sq, int64_t *s
 int rr_cnn_act(rr_dqn *dqn, const float *const params[8], const uint8_t *pixels, int32_t n, int32_t channels, float epsilon,
                uint64_t seed, uint32_t call, int32_t *actions, float *qvalues, void *stream);
 
+/* ---- the SAC agent's choose_action (roborugby_amd/csrc/rr_sac.hip, rr_sac.hpp; roborugby_amd/sac.py ActorNetwork / BatchedSACAgent):
+ * ActorNetwork.sample_normal (Training_SAC_pytorch.py:207-234) for n observations [n, 11] in one launch, on the fp32 matrix cores.
+ * n_actions = A = 2 * nr_happy of the thrust entry (rr_step_thrust): 2 or 4.
+ * params, in torch.nn.Linear layouts and fp32, read as they stand at call time (nothing is kept in the handle):
+ *   fc1.weight [256,11], fc1.bias [256], fc2.weight [256,256], fc2.bias [256], mu.weight [A,256], mu.bias [A], sigma.weight [A,256],
+ *   sigma.bias [A]
+ * THE ARITHMETIC (this is the specification; tests/sac_ref.py is it in numpy):
+ *   Forward.  ActorNetwork.forward (:192-205), fp32 throughout (rr_dqn_act's hidden layers: fp32 products summed in fp32, in no
+ *     particular order): mu [A] and the raw sigma outputs [A]; sigma = clamp(raw, 1e-6, 1).
+ *   Draw.  w0..w3 = Philox4x32-10 of counter (row, call, 0x5AC7, 0) under key (seed: low word, high word) -- rr_dqn_act's layout with
+ *     another stream word, so one (seed, call) never correlates the two.  For the pair (w0, w1): u1 = ((w0 >> 8) + 1) * 2^-24 in (0, 1],
+ *     u2 = (w1 >> 8) * 2^-24 in [0, 1), both exact in fp32; r = sqrtf(-2 logf(u1)), z0 = r cosf(2 pi u2), z1 = r sinf(2 pi u2).  The
+ *     pair (w2, w3) gives z2 and z3 the same way.  A = 2 uses z0 and z1.  Pass a fresh `call` every time.
+ *   Sample.  x_k = mu_k + sigma_k * z_k, actions[row][k] = max_action * tanhf(x_k),
+ *     log_prob[row] = sum_k [ -z_k^2 / 2 - logf(sigma_k) - log(2 pi) / 2 - logf(1 - a_k^2 + 1e-6) ] with a_k the SCALED action, as the
+ *     reference has it (:229-232).  With RR_SAC_DETERMINISTIC z = 0: actions = max_action * tanhf(mu), log_prob the formula at z = 0.
+ * Outputs: actions [n, A] is required; log_prob [n], head [n, 2A] (mu[0..A), then the RAW sigma outputs before the clamp) and noise
+ * [n, A] (the draws z; all 0 with RR_SAC_DETERMINISTIC) are each optional (NULL: not written).  Every element of every output that was
+ * passed is written; no row >= n is read or written.
+ * Returns -1 (message "rr_sac_act: ...": rr_dqn_last_error) and launches nothing for a null handle / params / params entry / obs /
+ * actions, an n that is not a positive multiple of 64, n_actions outside {2, 4}, a max_action that is not finite and > 0, unknown flag
+ * bits. */
+#define RR_SAC_DETERMINISTIC 1      /* actions = max_action * tanh(mu); noise, if given, is written as 0 */
+int rr_sac_act(rr_dqn *dqn, const float *const params[8], const float *obs, int32_t n, int32_t n_actions, float max_action,
+               int32_t flags, uint64_t seed, uint32_t call, float *actions, float *log_prob, float *head, float *noise, void *stream);
+
 /* ---- the frame-sharing pixel replay (roborugby_amd/csrc/rr_frames.hpp, rr_frames.hip; roborugby_amd/frame_replay.py FrameReplay): a ring
  * that stores every frame ONCE instead of two whole stacked observations per transition.  The caller owns the ring (device memory):
  *   frames  u8  [slots, rows, frame_bytes]   the newest frame of every row after push k, in slot k % slots

@@ -4,7 +4,7 @@ Product = the HIP library (csrc/, built in-tree as libroborugby_amd.so) behind t
 include/roborugby_amd.h, plus this thin Python mirror of the reference's gym.Env surface."""
 from .config import PRESETS, Preset  # noqa: F401
 
-__all__ = ["PRESETS", "Preset", "BatchedRoboRugbyEnv", "RoboRugbyEnv", "make", "Direction", "DebugInfo", "ShardedPipeline", "PixelObservation", "FrameReplay"]
+__all__ = ["PRESETS", "Preset", "BatchedRoboRugbyEnv", "RoboRugbyEnv", "make", "Direction", "DebugInfo", "ShardedPipeline", "PixelObservation", "FrameReplay", "BatchedSACAgent"]
 
 
 def __getattr__(name):  # torch / the HIP library are only needed once an env is actually used
@@ -20,4 +20,7 @@ def __getattr__(name):  # torch / the HIP library are only needed once an env is
     if name == "FrameReplay":
         from .frame_replay import FrameReplay
         return FrameReplay
+    if name == "BatchedSACAgent":
+        from .sac import BatchedSACAgent
+        return BatchedSACAgent
     raise AttributeError(name)

@@ -92,6 +92,7 @@ SYMBOLS = {
     "rr_dqn_store": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rr_dqn_act": (C.c_int, [_vp, C.POINTER(_vp * 6), _vp, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
     "rr_cnn_act": (C.c_int, [_vp, C.POINTER(_vp * 8), _vp, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
+    "rr_sac_act": (C.c_int, [_vp, C.POINTER(_vp * 8), _vp, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "rr_frames_push": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rr_frames_sample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_uint64,
                                    C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -100,6 +101,8 @@ SYMBOLS = {
     "rr_state_bytes_per_env": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "rr_lanes_per_env": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
 }
+
+RR_SAC_DETERMINISTIC = 1  # rr_sac_act's flag (include/roborugby_amd.h)
 
 _lib = None
 _lib_exact = None
@@ -255,3 +258,10 @@ class DqnHandle(_Handle):
         ptrs = (C.c_void_p * 6)(*[p.data_ptr() for p in params])
         self.call("rr_dqn_act", C.byref(ptrs), ptr(obs), n, float(min(max(epsilon, 0.0), 1.0)), int(seed), calls & 0xFFFFFFFF, ptr(actions),
                   ptr(q), self.stream() if stream is None else stream)
+
+    def sac_act(self, params, obs, n, n_actions, max_action, seed, calls, actions, deterministic=False, log_prob=None, head=None, noise=None):
+        """rr_sac_act on the actor `params` (its eight tensors): float32 [n, n_actions] squashed samples for the n rows of `obs`, the draws
+        keyed by (seed, row, the low 32 bits of `calls`); log_prob [n], head [n, 2 n_actions], noise [n, n_actions]: optionally written."""
+        ptrs = (C.c_void_p * 8)(*[p.data_ptr() for p in params])
+        self.launch("rr_sac_act", C.byref(ptrs), ptr(obs), n, n_actions, float(max_action), RR_SAC_DETERMINISTIC if deterministic else 0,
+                    int(seed) & 0xFFFFFFFFFFFFFFFF, calls & 0xFFFFFFFF, ptr(actions), ptr(log_prob), ptr(head), ptr(noise))

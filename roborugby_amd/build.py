@@ -15,10 +15,11 @@ SRC_KSTEP = os.path.join(HERE, "csrc", "rr_kstep_inst.hip")  # explicit instanti
 SRC_DQN = os.path.join(HERE, "csrc", "rr_dqn.hip")            # fused DQN update (config 5): its own translation unit
 SRC_CNN = os.path.join(HERE, "csrc", "rr_cnn.hip")            # the pixel agent's forward on the bf16 matrix cores (rr_cnn_act)
 SRC_FRAMES = os.path.join(HERE, "csrc", "rr_frames.hip")      # the frame-sharing pixel replay (rr_frames_push / rr_frames_sample)
+SRC_SAC = os.path.join(HERE, "csrc", "rr_sac.hip")            # the SAC actor's choose_action on the fp32 matrix cores (rr_sac_act)
 HDR_KSTEP = os.path.join(HERE, "csrc", "rr_kstep.hpp")         # ... and the table of built configurations
-DEPS = [SRC, SRC_KSTEP, SRC_DQN, SRC_CNN, SRC_FRAMES, HDR_KSTEP, os.path.join(HERE, "csrc", "rr_sim.hpp"), os.path.join(HERE, "csrc", "rr_dqn_shared.hpp"),
+DEPS = [SRC, SRC_KSTEP, SRC_DQN, SRC_CNN, SRC_FRAMES, SRC_SAC, HDR_KSTEP, os.path.join(HERE, "csrc", "rr_sim.hpp"), os.path.join(HERE, "csrc", "rr_dqn_shared.hpp"),
         os.path.join(HERE, "csrc", "rr_extras.hpp"), os.path.join(HERE, "csrc", "rr_hive.hpp"), os.path.join(HERE, "csrc", "rr_render.hpp"),
-        os.path.join(HERE, "csrc", "rr_frames.hpp"),
+        os.path.join(HERE, "csrc", "rr_frames.hpp"), os.path.join(HERE, "csrc", "rr_dqn_tile.hpp"), os.path.join(HERE, "csrc", "rr_sac.hpp"),
         os.path.join(os.path.dirname(HERE), "include", "roborugby_amd.h")]
 LIB = os.path.join(HERE, "libroborugby_amd.so")
 # the exact-trig parity build: the same sources with -DRR_EXACT_TRIG=1 (sin / cos of the robot kinematics in double-double, ~correctly
@@ -100,7 +101,7 @@ def build_hip_library(force=False, verbose=False, jobs=None, exact=False):
         units = [(SRC, ["-DRR_SPLIT_BUILD"], os.path.join(tmpd, "rr_kernels.o"))]
         units += [(SRC_KSTEP, [f"-DRR_PART={k}"], os.path.join(tmpd, f"rr_kstep_{k}.o")) for k in range(KSTEP_PARTS)]
         units += [(SRC_DQN, [], os.path.join(tmpd, "rr_dqn.o")), (SRC_CNN, [], os.path.join(tmpd, "rr_cnn.o")),
-                  (SRC_FRAMES, [], os.path.join(tmpd, "rr_frames.o"))]
+                  (SRC_FRAMES, [], os.path.join(tmpd, "rr_frames.o")), (SRC_SAC, [], os.path.join(tmpd, "rr_sac.o"))]
 
         def compile_one(u):
             src, defs, obj = u
@@ -164,7 +165,7 @@ def build_shape_library(nrh, nrg, nbp, nbn, force=False, verbose=False, exact=Fa
     tmp = lib_path + f".tmp{os.getpid()}"
     cmd = [find_hipcc()] + HIPCC_FLAGS + (["-DRR_EXACT_TRIG=1"] if exact else []) + [
         "-DRR_CUSTOM_SHAPE", "-DRR_CFG_SUBSET=9", f"-DRR_NRH={nrh}", f"-DRR_NRG={nrg}", f"-DRR_NBP={nbp}", f"-DRR_NBN={nbn}", f"-DRR_CVW={vw}",
-        "-o", tmp, SRC, SRC_DQN, SRC_CNN, SRC_FRAMES]
+        "-o", tmp, SRC, SRC_DQN, SRC_CNN, SRC_FRAMES, SRC_SAC]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

@@ -26,15 +26,13 @@
 
 #include "../../include/roborugby_amd.h"
 #include "rr_dqn_shared.hpp"
+#include "rr_dqn_tile.hpp"
 
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
+using namespace rr_tile; // H, IN, TM, LDX, NT, f16v, mfma, acc_row, hidden_tile
 
-constexpr int H = 256, IN = 11, NA = 8;
-constexpr int TM = 64;        // samples per tile
-constexpr int LDX = TM + 1;   // LDS row stride of the transposed activations (words)
-constexpr int NT = 256;       // threads per workgroup: 4 wavefronts, one per SIMD
+constexpr int NA = 8;
 // partial-gradient layout (floats), also the layout of the flat Adam moments
 constexpr int OFF_W2 = 0, OFF_W1 = OFF_W2 + H * H, OFF_W3 = OFF_W1 + H * IN, OFF_B1 = OFF_W3 + NA * H, OFF_B2 = OFF_B1 + H,
               OFF_B3 = OFF_B2 + H, OFF_LOSS = OFF_B3 + NA, P_COUNT = OFF_LOSS, P_STRIDE = ((OFF_LOSS + 1 + 63) / 64) * 64;
@@ -49,80 +47,9 @@ struct Batch {
     float gamma;
 };
 
-__device__ __forceinline__ f16v mfma(float a, float b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-// row of a 32 x 32 accumulator tile held in register r of a lane in half `half` (lanes 32-63: half = 1); its column is lane & 31
-__device__ __forceinline__ int acc_row(int r, int half) { return 8 * (r >> 2) + 4 * half + (r & 3); }
-
-// hidden layers of one net for the tile in Sb ([12][LDX], row 11 = 0): X0 = relu(fc1), X1 = relu(fc2), Q[a][m] = fc3
+// hidden layers of one net for the tile in Sb ([12][LDX], row 11 = 0): X0 = relu(fc1), X1 = relu(fc2) (rr_dqn_tile.hpp), Q[a][m] = fc3
 __device__ __forceinline__ void forward_tile(const Net &net, const float *Sb, float *X0, float *X1, float *Q, int w, int half, int c, int l) {
-    f16v acc[4];
-    // ---- fc1: K = 11 (padded to 12), output tiles: n-tiles {2w, 2w+1} x m-tiles {0, 1}
-#pragma unroll
-    for (int q = 0; q < 4; q++) acc[q] = (f16v)0.0f;
-#pragma unroll
-    for (int p = 0; p < 6; p++) {
-        const int k = 2 * p + half;
-        const float a0 = Sb[k * LDX + c], a1 = Sb[k * LDX + 32 + c];
-#pragma unroll
-        for (int nt = 0; nt < 2; nt++) {
-            const int n = (2 * w + nt) * 32 + c;
-            const float b = k < IN ? net.w1[n * IN + k] : 0.0f;
-            acc[nt * 2 + 0] = mfma(a0, b, acc[nt * 2 + 0]);
-            acc[nt * 2 + 1] = mfma(a1, b, acc[nt * 2 + 1]);
-        }
-    }
-#pragma unroll
-    for (int nt = 0; nt < 2; nt++) {
-        const int n = (2 * w + nt) * 32 + c;
-        const float bias = net.b1[n];
-#pragma unroll
-        for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const float v = acc[nt * 2 + mt][r] + bias;
-                X0[n * LDX + mt * 32 + acc_row(r, half)] = v > 0.0f ? v : 0.0f;
-            }
-    }
-    __syncthreads();
-    // ---- fc2: K = 256, eight k per round: a lane's float4 of W2 covers k = 8 kg + 4 half .. + 3 (the two halves of the
-    // wavefront are the two k slots of an MFMA; which k a slot holds is free as long as A and B agree)
-#pragma unroll
-    for (int q = 0; q < 4; q++) acc[q] = (f16v)0.0f;
-    float4 bw[2], bw_next[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; nt++) bw[nt] = *reinterpret_cast<const float4 *>(&net.w2[((2 * w + nt) * 32 + c) * H + 4 * half]);
-#pragma unroll 2
-    for (int kg = 0; kg < H / 8; kg++) {
-        const int kb = kg * 8 + 4 * half;
-        if (kg + 1 < H / 8) {
-#pragma unroll
-            for (int nt = 0; nt < 2; nt++) bw_next[nt] = *reinterpret_cast<const float4 *>(&net.w2[((2 * w + nt) * 32 + c) * H + kb + 8]);
-        }
-        const float bv[2][4] = { { bw[0].x, bw[0].y, bw[0].z, bw[0].w }, { bw[1].x, bw[1].y, bw[1].z, bw[1].w } };
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float a0 = X0[(kb + j) * LDX + c], a1 = X0[(kb + j) * LDX + 32 + c];
-#pragma unroll
-            for (int nt = 0; nt < 2; nt++) {
-                acc[nt * 2 + 0] = mfma(a0, bv[nt][j], acc[nt * 2 + 0]);
-                acc[nt * 2 + 1] = mfma(a1, bv[nt][j], acc[nt * 2 + 1]);
-            }
-        }
-        bw[0] = bw_next[0]; bw[1] = bw_next[1];
-    }
-#pragma unroll
-    for (int nt = 0; nt < 2; nt++) {
-        const int n = (2 * w + nt) * 32 + c;
-        const float bias = net.b2[n];
-#pragma unroll
-        for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const float v = acc[nt * 2 + mt][r] + bias;
-                X1[n * LDX + mt * 32 + acc_row(r, half)] = v > 0.0f ? v : 0.0f;
-            }
-    }
-    __syncthreads();
+    hidden_tile(net, Sb, X0, X1, w, half, c);
     // ---- fc3 (8 outputs: VALU): wavefront w computes actions 2w, 2w+1 for sample m = lane; the weights are wave-uniform
     {
         const float *w3a = net.w3 + (2 * w) * H, *w3b = net.w3 + (2 * w + 1) * H;

@@ -1,5 +1,5 @@
 // rr_dqn_shared.hpp -- what the translation units behind the rr_dqn handle share (rr_dqn.hip: the lidar agent's fused kernels;
-// rr_cnn.hip: the pixel agent's forward): the handle itself, the error string's setter and the epsilon-greedy draw, so that
+// rr_cnn.hip: the pixel agent's forward; rr_sac.hip: the SAC actor's, whose draws take the Philox rounds below): the handle itself, the error string's setter and the epsilon-greedy draw, so that
 // rr_dqn_act and rr_cnn_act explore the same rows with the same actions under one (seed, call).
 // The handle, the setter's declaration and the Philox rounds are plain C++ as well: csrc/rr_frames.hpp's host emulation includes this.
 #pragma once

@@ -1,0 +1,45 @@
+// rr_sac.hpp -- the per-row arithmetic of rr_sac_act's epilogue (include/roborugby_amd.h is the specification): the standard normal
+// draws of a row, the clamp of sigma, the squashed action and a component's share of the log-probability.  Plain C++ as well as HIP:
+// tests/emu/rr_sac_emu.cpp compiles these very functions with g++ and holds them to tests/sac_ref.py without a GPU.
+#pragma once
+#include <math.h>
+#include "rr_dqn_shared.hpp"
+
+namespace rr {
+
+constexpr uint32_t SAC_STREAM = 0x5AC7u;  // counter word 2 of the draws (rr_dqn_act / rr_cnn_act: 0x0AC7, rr_frames_sample: 0x5A3E)
+constexpr float SAC_SIGMA_MIN = 1e-6f, SAC_SIGMA_MAX = 1.0f;  // ActorNetwork.forward: clamp(sigma, reparam_noise, 1)
+constexpr float SAC_LOG_EPS = 1e-6f;                          // ... sample_normal: log(1 - a^2 + reparam_noise)
+constexpr float SAC_TWO_PI = 6.2831853071795865f, SAC_HALF_LOG_TWO_PI = 0.91893853320467274f;
+constexpr float SAC_2M24 = 5.9604644775390625e-8f;
+
+// two 32-bit words -> u1 in (0, 1], u2 in [0, 1): multiples of 2^-24, exact in fp32
+RR_DQN_HD void sac_uniforms(uint32_t wa, uint32_t wb, float &u1, float &u2) {
+    u1 = (float)((wa >> 8) + 1u) * SAC_2M24;
+    u2 = (float)(wb >> 8) * SAC_2M24;
+}
+// Box-Muller: two independent standard normals from (u1, u2)
+RR_DQN_HD void sac_box_muller(float u1, float u2, float &z0, float &z1) {
+    const float r = sqrtf(-2.0f * logf(u1)), a = SAC_TWO_PI * u2;
+    z0 = r * cosf(a);
+    z1 = r * sinf(a);
+}
+// the four draws of row `row` in call `call`: Philox4x32-10, counter (row, call, SAC_STREAM, 0), key = seed (low word, high word)
+RR_DQN_HD void sac_draw(uint32_t row, uint32_t call, uint64_t seed, float z[4]) {
+    uint32_t w[4] = { row, call, SAC_STREAM, 0u };
+    philox4x32_10(w, (uint32_t)seed, (uint32_t)(seed >> 32));
+    float u1, u2;
+    sac_uniforms(w[0], w[1], u1, u2);
+    sac_box_muller(u1, u2, z[0], z[1]);
+    sac_uniforms(w[2], w[3], u1, u2);
+    sac_box_muller(u1, u2, z[2], z[3]);
+}
+// torch.clamp(raw, 1e-6, 1): a NaN stays a NaN
+RR_DQN_HD float sac_sigma(float raw) { return raw < SAC_SIGMA_MIN ? SAC_SIGMA_MIN : (raw > SAC_SIGMA_MAX ? SAC_SIGMA_MAX : raw); }
+RR_DQN_HD float sac_action(float mu, float sigma, float z, float max_action) { return max_action * tanhf(mu + sigma * z); }
+// Normal(mu, sigma).log_prob(mu + sigma z) - log(1 - a^2 + 1e-6) of one component (a: the SCALED action, as the reference has it)
+RR_DQN_HD float sac_log_prob_term(float sigma, float z, float a) {
+    return -0.5f * z * z - logf(sigma) - SAC_HALF_LOG_TWO_PI - logf(1.0f - a * a + SAC_LOG_EPS);
+}
+
+} // namespace rr

@@ -224,7 +224,8 @@ class BatchedSACAgent:
         """One Agent.learn (:322-388): a batch drawn with replacement, the value, actor and critic steps in that order, the soft update.
         Each loss only steps its own network(s), and none depends on what an earlier step of the same call changed (the actor loss not on
         the value net, the critic loss on neither), so the three are computed on one forward and stepped in the reference's order.
-        Returns the three losses (device scalars), None until the replay holds a batch."""
+        Returns the three losses (device scalars), None until the replay holds a batch.
+        The draws are made here -- the batch rows, then the value target's noise, then the actor loss's -- and learn_on does the rest."""
         if self.mem_cntr < self.batch_size:
             return None
         max_mem = min(self.mem_cntr, self.mem_size)
@@ -233,6 +234,11 @@ class BatchedSACAgent:
         shape = (self.batch_size, self.n_actions)
         noise_value = torch.randn(shape, generator=self.gen, device=self.device)
         noise_actor = torch.randn(shape, generator=self.gen, device=self.device)
+        return self.learn_on(batch, noise_value, noise_actor)
+
+    def learn_on(self, batch, noise_value, noise_actor):
+        """learn() after its draws, a function of the agent's state and its arguments alone: the losses of batch = (state, action, reward,
+        new_state, done) under the two standard normal tensors [B, A], the value, actor and critic steps, the soft update, the counters."""
         value_loss, actor_loss, critic_loss = self.losses(batch, noise_value, noise_actor)
         for loss, opt in ((value_loss, self.value_optimizer), (actor_loss, self.actor_optimizer), (critic_loss, self.critic_optimizer)):
             opt.zero_grad(set_to_none=True)

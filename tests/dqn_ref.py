@@ -4,7 +4,9 @@ code.  tests/test_dqn_ref.py checks these yardsticks themselves (no GPU); tests/
   philox4x32_10 / act_draw   the epsilon draw of rr_dqn_act as the kernel lays it out today (checkpoints carry `act_calls`, so the
                              layout is part of what a resumed run depends on)
   ring_store                 DQNAgent.store_transition (Training_DQN_pytorch.py:126-136) row by row
-  forward64 / adam64         the network's forward and torch.optim.Adam's step (no weight decay, no amsgrad) in float64"""
+  forward64 / adam64         the network's forward and torch.optim.Adam's step (no weight decay, no amsgrad) in float64
+  learn_grads64              the loss of DQNAgent.learn (Training_DQN_pytorch.py:166-184) and its gradient in float64
+                             (tests/test_agent_reference.py holds it to the reference trainer's own float64 run)"""
 import numpy as np
 import torch
 
@@ -93,6 +95,22 @@ def forward64(params, x):
     h1 = torch.clamp(x @ w1.t() + b1, min=0.0)
     h2 = torch.clamp(h1 @ w2.t() + b2, min=0.0)
     return h2 @ w3.t() + b3
+
+
+def learn_grads64(eval_params, target_params, batch, gamma):
+    """(loss, [gradient per eval parameter, in their order]) of DQNAgent.learn's loss in float64.  batch = (state, action, reward,
+    new_state, done): q_eval = Q_eval(state)[row, action]; q_next = Q_target(new_state) with the whole ROW of a terminal sample set to
+    0 before the max; q_target = reward + gamma * max_a q_next, a constant; loss = the mean over the batch of (q_target - q_eval)^2"""
+    state, action, reward, new_state, done = (torch.as_tensor(np.asarray(t)) for t in batch)
+    leaves = [torch.as_tensor(np.asarray(p)).double().clone().requires_grad_(True) for p in eval_params]
+    w1, b1, w2, b2, w3, b3 = leaves
+    h = torch.clamp(torch.clamp(state.double() @ w1.t() + b1, min=0.0) @ w2.t() + b2, min=0.0)
+    q_eval = (h @ w3.t() + b3)[torch.arange(state.shape[0]), action.long()]
+    q_next = forward64(target_params, new_state)
+    q_next[done.bool()] = 0.0
+    q_target = reward.double() + gamma * q_next.max(dim=1)[0]
+    loss = ((q_target - q_eval) ** 2).mean()
+    return float(loss.detach()), [g.numpy() for g in torch.autograd.grad(loss, leaves)]
 
 
 def adam64(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8):

@@ -1,6 +1,7 @@
 """Host-only references for the SAC actor kernel (roborugby_amd/csrc/rr_sac.hip, rr_sac.hpp) and the SAC agent (roborugby_amd/sac.py):
 numpy / torch-CPU, none of the project's kernel code.  tests/test_sac_ref.py checks these yardsticks themselves (no GPU);
-tests/test_sac_emulated.py holds the g++ build of csrc/rr_sac.hpp to them and tests/test_gpu_sac_act.py the kernel.
+tests/test_sac_emulated.py holds the g++ build of csrc/rr_sac.hpp to them and tests/test_gpu_sac_act.py the kernel;
+tests/test_agent_reference.py holds actor_head64, squash64 and losses64 to the reference trainer's own float64 run (tests/golden/sac_*.npz).
 
   words / uniforms / draw64      rr_sac_act's draw as include/roborugby_amd.h specifies it, in float64
   actor_head64                   ActorNetwork.forward up to (mu, raw sigma) in float64

@@ -21,7 +21,10 @@ RR_TrashyPhysics.py:323-335, made on the ball's rect before the call).  They get
 kat and no thrust part: neither reads the arena size beyond what the trajectories'
 lidar observations cover.
 
-usage:  python oracle/refgen/gen_golden.py [G|T|D|X|Dwide|Ttall|all] [parts...]
+The limit shapes W (1 + 1 robots, 4 + 7 balls) and R (4 + 4 robots, 2 + 2 balls) get the
+parts reset and traj, the latter with shorter episodes (11 balls / 8 robots per state).
+
+usage:  python oracle/refgen/gen_golden.py [G|T|D|X|W|R|Dwide|Ttall|all] [parts...]
 One preset per process (constants are module globals in the reference), so
 `all` re-invokes this script once per preset.
 """
@@ -266,8 +269,13 @@ def gen_traj(R, preset):
     reset_scratch_rect(R)
     NR = len(env.lstRobots)
     base = BASE.get(preset, preset)  # a non-square id runs its base preset's plan from its base preset's seed
-    rng = random.Random({"G": 20201, "T": 20202, "D": 20203, "X": 20204}[base])
-    if base in ("D", "X"):  # two robots (one per team), two balls (one of each colour), G's arena and episode length
+    rng = random.Random({"G": 20201, "T": 20202, "D": 20203, "X": 20204, "W": 20205, "R": 20206}[base])
+    if base in ("W", "R"):  # the limit shapes (11 balls / 8 robots): D's plan with the episodes cut short, so that the file stays below X's size
+        plan = [("random", NR, 100, False, 0), ("chase", NR, 160, False, 0), ("chase_noisy", NR, 160, True, 6.0),
+                ("chase", NR, 160, True, 9.0), ("forward", NR, 120, True, 3.0), ("chase", 1, 120, True, 5.0),
+                ("chase_noisy", NR, 160, True, 12.0), ("chase", NR, 160, True, 2.0), ("random", NR, 120, True, 10.0),
+                ("chase", NR, 160, False, 0), ("chase_noisy", NR, 160, True, 4.0), ("chase", NR, 160, True, 7.0)]
+    elif base in ("D", "X"):  # two robots (one per team), two balls (one of each colour), G's arena and episode length
         plan = [("random", NR, 150, False, 0), ("chase", NR, 300, False, 0), ("chase_noisy", NR, 300, True, 6.0),
                 ("chase", NR, 300, True, 9.0), ("forward", NR, 200, True, 3.0), ("chase", 1, 300, True, 5.0),
                 ("chase_noisy", NR, 300, True, 12.0), ("chase", NR, 300, True, 2.0), ("random", NR, 200, True, 10.0),
@@ -729,13 +737,13 @@ def main():
     if which == "all":
         for p in ("T", "G", "D", "X"):
             subprocess.check_call([sys.executable, os.path.abspath(__file__), p])
-        for p, parts in (("Dwide", ["reset", "traj", "mix"]), ("Ttall", ["reset", "traj"])):
+        for p, parts in (("Dwide", ["reset", "traj", "mix"]), ("Ttall", ["reset", "traj"]), ("W", ["reset", "traj"]), ("R", ["reset", "traj"])):
             subprocess.check_call([sys.executable, os.path.abspath(__file__), p] + parts)
         return
     from load_reference import load_reference
     R = load_reference(which)
     os.makedirs(GOLD, exist_ok=True)
-    parts = sys.argv[2:] or (["reset", "traj"] if which in BASE else ["kat", "reset", "traj"])
+    parts = sys.argv[2:] or (["reset", "traj"] if which in BASE or which in ("W", "R") else ["kat", "reset", "traj"])
     assert which not in BASE or not {"kat", "thrust"} & set(parts), "the non-square ids have no kat and no thrust part"
     if "kat" in parts:
         gen_kat(R, which)

@@ -7,7 +7,9 @@ RR_Constants.py with that one assignment flipped into a module object that is
 registered before anything else imports it.  Preset D (the 1+1 / 1+1 duel) keeps
 GAME_MODE = True and sets the four entity counts of RR_Constants.py:30-34 to 1 the
 same way; preset X sets them to 2 + 1 robots and 2 + 3 balls (a shape outside the
-library's built list: odd counts, unequal teams).  The non-square ids of ARENA
+library's built list: odd counts, unequal teams), W to 1 + 1 robots and 4 + 7 balls,
+R to 4 + 4 robots and 2 + 2 balls (the limits of the one-shape library: 11 balls,
+8 robots, 32 ball-robot pairs).  The non-square ids of ARENA
 (Dwide: D at 1000 x 640, Ttall: T at 480 x 720) replace the two arena-size
 assignments of RR_Constants.py:6-7 the same way, on top of their base preset's
 patches; the sizes are integers, as the reference's own are (its reset draws them
@@ -18,6 +20,8 @@ import sys
 import types
 
 REF_ROOT = os.environ.get("RR_REFERENCE_ROOT", "/root/reference")
+# (NUM_ROBOTS_HAPPY, NUM_ROBOTS_GRUMPY, NUM_BALL_POS, NUM_BALL_NEG) patched in; G and T keep the reference's own
+COUNTS = {"D": (1, 1, 1, 1), "X": (2, 1, 2, 3), "W": (1, 1, 4, 7), "R": (4, 4, 2, 2)}
 BASE = {"Dwide": "D", "Ttall": "T"}                    # preset whose constants and entity counts the id keeps
 ARENA = {"Dwide": (1000, 640), "Ttall": (480, 720)}    # (ARENA_WIDTH, ARENA_HEIGHT) patched in; every other id keeps the reference's
 
@@ -27,9 +31,10 @@ def reference_available():
 
 
 def load_reference(preset):
-    """Returns a namespace with the reference modules for preset 'G', 'T', 'D', 'X' or one of the non-square ids of ARENA."""
+    """Returns a namespace with the reference modules for preset 'G', 'T', 'D', 'X', 'W', 'R' or one of the non-square ids of ARENA."""
     ident, preset = preset, BASE.get(preset, preset)
-    assert preset in ("G", "T", "D", "X")
+    assert preset in ("G", "T") or preset in COUNTS
+    counts = COUNTS.get(preset, (2, 2, 4, 4) if preset == "G" else (1, 0, 1, 0))
     arena = ARENA.get(ident)
     if not reference_available():
         raise RuntimeError("reference tree not present at %s" % REF_ROOT)
@@ -43,11 +48,11 @@ def load_reference(preset):
         sys.path.insert(0, REF_ROOT)
     if "robo_rugby.gym_env.RR_Constants" in sys.modules:
         const = sys.modules["robo_rugby.gym_env.RR_Constants"]
-        have = {4: "G", 2: "D", 3: "X"}[const.NUM_ROBOTS_TOTAL] if const.GAME_MODE else "T"
+        have = (bool(const.GAME_MODE), const.NUM_ROBOTS_HAPPY, const.NUM_ROBOTS_GRUMPY, const.NUM_BALL_POS, const.NUM_BALL_NEG)
         size = (const.ARENA_WIDTH, const.ARENA_HEIGHT)
-        if have != preset or size != (arena or ((800, 800) if const.GAME_MODE else (600, 600))):
-            raise RuntimeError("reference already loaded with preset %s at %d x %d in this process" % ((have,) + size))
-    elif preset in ("T", "D", "X"):  # (every id of ARENA is based on one of these)
+        if have != (preset != "T",) + counts or size != (arena or ((800, 800) if const.GAME_MODE else (600, 600))):
+            raise RuntimeError("reference already loaded with other constants (%s at %d x %d) in this process" % ((have,) + size))
+    elif preset != "G":  # (every id of ARENA is based on one of these)
         pkg = types.ModuleType("robo_rugby")
         pkg.__path__ = [os.path.join(REF_ROOT, "robo_rugby")]
         sub = types.ModuleType("robo_rugby.gym_env")
@@ -57,9 +62,8 @@ def load_reference(preset):
         if preset == "T":
             assert text.count("GAME_MODE = True") == 1
             text = text.replace("GAME_MODE = True", "GAME_MODE = False", 1)
-        else:  # D, the duel: one robot per team, one ball of each colour; X: 2 + 1 robots, 2 + 3 balls
-            want = dict(NUM_BALL_POS=1, NUM_BALL_NEG=1, NUM_ROBOTS_HAPPY=1, NUM_ROBOTS_GRUMPY=1) if preset == "D" else \
-                dict(NUM_BALL_POS=2, NUM_BALL_NEG=3, NUM_ROBOTS_HAPPY=2, NUM_ROBOTS_GRUMPY=1)
+        else:  # the four entity counts of COUNTS
+            want = dict(zip(("NUM_ROBOTS_HAPPY", "NUM_ROBOTS_GRUMPY", "NUM_BALL_POS", "NUM_BALL_NEG"), counts))
             for name, was in (("NUM_BALL_POS", "4 if GAME_MODE else 1"), ("NUM_BALL_NEG", "4 if GAME_MODE else 0"),
                               ("NUM_ROBOTS_HAPPY", "2 if GAME_MODE else 1"), ("NUM_ROBOTS_GRUMPY", "2 if GAME_MODE else 0")):
                 line = f"{name} = {was}"
@@ -87,8 +91,9 @@ def load_reference(preset):
     import robo_rugby.gym_env.RR_Goal as goal
     import robo_rugby.gym_env.RR_ScoreKeepers as sk
     import robo_rugby.gym_env.RR_Observers as obs
-    assert bool(const.GAME_MODE) == (preset in ("G", "D", "X"))
-    assert const.NUM_ROBOTS_TOTAL == {"G": 4, "T": 1, "D": 2, "X": 3}[preset]
+    assert bool(const.GAME_MODE) == (preset != "T")
+    assert (const.NUM_ROBOTS_HAPPY, const.NUM_ROBOTS_GRUMPY, const.NUM_BALL_POS, const.NUM_BALL_NEG) == counts
+    assert const.NUM_ROBOTS_TOTAL == counts[0] + counts[1]
     assert arena is None or (const.ARENA_WIDTH, const.ARENA_HEIGHT) == arena
     ns = types.SimpleNamespace(MyUtils=MyUtils, const=const, base=base, tp=tp, envs=envs, robot=robot,
                                ball=ball, goal=goal, sk=sk, obs=obs, preset=ident)

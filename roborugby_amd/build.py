@@ -128,13 +128,21 @@ def build_hip_library(force=False, verbose=False, jobs=None, exact=False):
 SHAPES_DIR = os.path.join(HERE, "shapes")
 
 
-def shape_lanes(nrh, nrg, nbp, nbn):
-    """lanes per arena of a one-shape library: one lane per entity, a power of two >= 2; raises for counts the phases' masks cannot hold"""
+def shape_lanes(nrh, nrg, nbp, nbn, exact=False):
+    """lanes per arena of a one-shape library: one lane per entity, a power of two >= 2; ValueError, naming the limit, for every shape the
+    kernel sources refuse to compile (`exact`: as the parity build).  The Python statement of csrc/rr_sim.hpp's constexpr shape_lanes:
+    tests/test_shape_limits.py holds the two to each other over the whole grid of counts."""
     nr, nb = nrh + nrg, nbp + nbn
-    if min(nrh, nrg, nbp, nbn) < 0 or nrh < 1 or nb < 1 or nbp < 1:
+    if min(nrh, nrg, nbp, nbn) < 0 or nrh < 1 or nbp < 1:
         raise ValueError("at least one happy robot and one positive ball (the observation and the rewards are built around them)")
     if nr > 8 or nb > 11 or nr * nb > 32:
         raise ValueError(f"{nr} robots x {nb} balls: the contact masks hold at most 8 robots, 11 balls and 32 ball-robot pairs per arena")
+    if nbp * (1 + nr) > 6 * nr:
+        raise ValueError(f"{nbp} positive balls with {nr} robot{'s' if nr > 1 else ''}: the step's reward scratch holds at most 6 NR / (NR + 1) "
+                         f"positive balls ({6 * nr // (nr + 1)} here: it reuses the robots' lidar slots)")
+    if exact and nr < 2 and nb != 1:
+        raise ValueError(f"one robot with {nb} balls: the parity build (exact_trig) carries the reference's scratch rect for one robot "
+                         "only with one ball; the default build takes this shape")
     vw = 2
     while vw < max(nr, nb):
         vw *= 2
@@ -156,7 +164,7 @@ def shape_is_stale(nrh, nrg, nbp, nbn, exact=False):
 def build_shape_library(nrh, nrg, nbp, nbn, force=False, verbose=False, exact=False):
     """hipcc ... -DRR_CUSTOM_SHAPE -> roborugby_amd/shapes/libroborugby_amd_<nrh>x<nrg>_<nbp>x<nbn>.so: the same sources and ABI for ONE
     shape (fp64 and fp32-state precisions, every k_step variant), one translation unit, a minute or two of hipcc for G-sized shapes."""
-    vw = shape_lanes(nrh, nrg, nbp, nbn)
+    vw = shape_lanes(nrh, nrg, nbp, nbn, exact)
     lib_path = shape_lib_path(nrh, nrg, nbp, nbn, exact)
     if not force and not shape_is_stale(nrh, nrg, nbp, nbn, exact):
         return lib_path

@@ -381,6 +381,22 @@ template <typename R> RR_HD R angle_degrees(V2<R> a, V2<R> b, int &st) {
 struct F32State {};
 template <typename T> struct Precision { using Real = T; using Store = T; };
 template <> struct Precision<F32State> { using Real = double; using Store = float; };
+// The shapes these sources can be built for, stated once: lanes per arena of nrh + nrg robots and nbp + nbn balls (one lane per entity,
+// a power of two >= 2), or 0 for a shape they refuse.  `carry`: the parity build (RR_CARRY).  Cfg asserts it; the asserts at the sites
+// each limit comes from stay there.  roborugby_amd/build.py's shape_lanes says the same in Python, before any compiler runs
+// (tests/test_shape_limits.py sweeps the two against each other through the host emulation's export).
+constexpr int shape_lanes(int nrh, int nrg, int nbp, int nbn, bool carry) {
+    const int nr = nrh + nrg, nb = nbp + nbn;
+    if (nrh < 1 || nrg < 0 || nbp < 1 || nbn < 0) return 0; // the observation and the rewards are built around a happy robot and a positive ball
+    if (nr > 8) return 0;                  // status bits 16..23 name the robots NaughtyBots flagged
+    if (nb > 11) return 0;                 // the ball-pair mask is 64-bit: 11 balls make 55 pairs, 12 make 66
+    if (nr * nb > 32) return 0;            // the ball-robot pair mask is 32-bit
+    if (nbp * (1 + nr) > 6 * nr) return 0; // step_arena's reward scratch (NBP + NR * NBP values) reuses the 2 * 3 * NR lidar slots
+    if (carry && nr < 2 && nb != 1) return 0; // the parity build's one-robot carry chain is written for one ball (carry_quiet_sweep)
+    int vw = 2;
+    while (vw < nr || vw < nb) vw *= 2;
+    return vw;
+}
 template <int NRH_, int NRG_, int NBP_, int NBN_, typename Prec_, int VW_ = 64> struct Cfg {
     static constexpr int NRH = NRH_, NRG = NRG_, NBP = NBP_, NBN = NBN_;
     static constexpr int NR = NRH_ + NRG_, NB = NBP_ + NBN_;
@@ -393,6 +409,8 @@ template <int NRH_, int NRG_, int NBP_, int NBN_, typename Prec_, int VW_ = 64> 
     static_assert(VW == 2 || VW == 4 || VW == 8 || VW == 16 || VW == 32 || VW == 64, "VW must divide the wavefront");
     static_assert(NR >= 1 && NR <= VW && NB >= 1 && NB <= VW, "one lane per entity");
     static_assert(NB * NR <= 32 && NPB <= 64 && NB <= 16 && NR <= 16, "pair masks are 32/64-bit, per-ball masks 16-bit");
+    static_assert(shape_lanes(NRH_, NRG_, NBP_, NBN_, RR_CARRY != 0) != 0, "shape_lanes refuses these entity counts in this build");
+    static_assert(shape_lanes(NRH_, NRG_, NBP_, NBN_, RR_CARRY != 0) <= VW_, "fewer lanes per arena than shape_lanes asks for");
 };
 
 template <typename R> struct SimParams {

@@ -52,9 +52,10 @@ def oracle_step(preset, robots_xyr, balls_xyv, actions):
     return res, o.get_state()
 
 
-def make_corner_states(preset, n, seed):
+def make_corner_states(preset, n, seed, min_gap=0.0):
     """Balls around robot corners: at 6.4-7.7 px from a corner, in and next to the 7 x 7 square beyond BOTH side lines where only
-    the corner's radius test can hit (rr_sim.hpp: ball_near_robot's corner-zone bound) -- touching, grazing and just clear."""
+    the corner's radius test can hit (rr_sim.hpp: ball_near_robot's corner-zone bound) -- touching, grazing and just clear.
+    min_gap: robot centres are re-drawn until they are at least this far apart (0: wherever they fall)."""
     cfg = ol.PRESETS[preset]
     nr, nb = cfg["nr_h"] + cfg["nr_g"], cfg["nb_p"] + cfg["nb_n"]
     W, H = cfg["W"], cfg["H"]
@@ -65,6 +66,8 @@ def make_corner_states(preset, n, seed):
         for r in range(nr):
             robots[a, r] = [rng.uniform(80, W - 80), rng.uniform(80, H - 80),
                             rng.choice([0, 90, 180, 270, rng.uniform(0, 360), float(rng.randint(0, 361))])]
+            while min_gap > 0 and r > 0 and np.hypot(*(robots[a, :r, :2] - robots[a, r, :2]).T).min() < min_gap:
+                robots[a, r, :2] = [rng.uniform(80, W - 80), rng.uniform(80, H - 80)]
         for b in range(nb):
             r = rng.randint(nr)
             rot = np.radians(robots[a, r, 2])

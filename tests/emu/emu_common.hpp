@@ -43,13 +43,15 @@ template <typename R> static inline void emu_fill_params(rr::SimParams<R> &sp, d
 }
 
 // The configurations the hive emulations are built for: X(preset, NRH, NRG, NBP, NBN, precision, f32, lanes per arena).
-// preset 0 T, 1 G, 2 D, 3 X (2 + 1 robots, 2 + 3 balls); f32: arithmetic in fp32 (G only)
+// preset 0 T, 1 G, 2 D, 3 X (2 + 1 robots, 2 + 3 balls), 5 W (1 + 1, 4 + 7: 11 balls at 16 lanes), 6 R (4 + 4, 2 + 2: 8 robots) -- the ids
+// of tests/emu_build.py; f32: arithmetic in fp32 (G only)
 #define EMU_HIVE_TABLE(X)                                                                                                             \
     X(0, 1, 0, 1, 0, double, 0, 2) X(0, 1, 0, 1, 0, double, 0, 4) X(0, 1, 0, 1, 0, double, 0, 64)                                      \
     X(1, 2, 2, 4, 4, double, 0, 8) X(1, 2, 2, 4, 4, double, 0, 16) X(1, 2, 2, 4, 4, double, 0, 32) X(1, 2, 2, 4, 4, double, 0, 64)     \
     X(1, 2, 2, 4, 4, float, 1, 8) X(1, 2, 2, 4, 4, float, 1, 64)                                                                       \
     X(2, 1, 1, 1, 1, double, 0, 4) X(2, 1, 1, 1, 1, double, 0, 64)                                                                     \
-    X(3, 2, 1, 2, 3, double, 0, 8) X(3, 2, 1, 2, 3, double, 0, 64)
+    X(3, 2, 1, 2, 3, double, 0, 8) X(3, 2, 1, 2, 3, double, 0, 64)                                                                     \
+    X(5, 1, 1, 4, 7, double, 0, 16) X(5, 1, 1, 4, 7, double, 0, 64) X(6, 4, 4, 2, 2, double, 0, 8) X(6, 4, 4, 2, 2, double, 0, 64)
 // f(Cfg<...>{}) of the row (preset, vw, f32), as dispatch() of rr_kernels.hip; -1: the row is not built
 template <class F> static inline int emu_hive_dispatch(int preset, int vw, int f32, F &&f) {
 #define X(p_, a, b, c, d, R_, f_, v_) \

@@ -53,28 +53,44 @@ template <class C> static void set_state(Emu<C> *e, const double *robots, const 
     derive(A, e->sp);
 }
 
-// The built kinds: X(handle kind, name, NRH, NRG, NBP, NBN, precision, lanes per arena).
-//   n:    narrow virtual waves: the same phases run in several rounds of VW lanes (what the packed GPU builds execute)
+// The built kinds: X(handle kind, name, preset, mode, NRH, NRG, NBP, NBN, precision, lanes per arena).  emu_create picks the row of
+// (preset, mode); every other use switches on the kind.
+//   preset: the ids of tests/emu_build.py (0 T, 1 G, 2 D, 3 X, 4 Y, 5 W, 6 R, 7 Q, 8 P)
+//   mode:   0 = fp64 at 64 lanes, 1 = fp32 at 64 lanes, 2 = fp64 in narrow virtual waves (names ...n): the same phases run in several
+//           rounds of VW lanes (what the packed GPU builds execute)
 //   D:    the duel shape (1 + 1 robots, 1 + 1 balls)
 //   X:    a shape that is NOT one of the library's built ones (2 + 1 robots, 2 + 3 balls: odd counts, unequal teams): what
 //         build_shape_library compiles on demand (roborugby_amd/build.py); one lane per entity needs 8 lanes
 //   Y:    one that packs at FOUR lanes per arena (1 + 1 robots, 2 + 1 balls): the narrow phases' "fewer than eight lanes" variants with
 //         more than one ball, a combination none of the built shapes has
+//   W, R, Q, P: the shapes at the limits of rr::shape_lanes (tests/oracle_lib.py: PRESETS), each at 64 lanes and at its own width:
+//         W 1 + 1 / 4 + 7 (16 lanes: 11 balls, 55 ball pairs), R 4 + 4 / 2 + 2 (8 robots, 32 ball-robot pairs), Q 2 + 2 / 3 + 3
+//         (observe_both's aliasing bound at equality), P 1 + 0 / 3 + 0 (the reward scratch's bound at equality; one robot with several
+//         balls, which the parity build refuses: EMU_KINDS_P is empty there)
+#if RR_CARRY
+#define EMU_KINDS_P(X, ...)
+#else
+#define EMU_KINDS_P(X, ...) X(19, CP64, 8, 0, 1, 0, 3, 0, double, 64, __VA_ARGS__) X(20, CP64n, 8, 2, 1, 0, 3, 0, double, 4, __VA_ARGS__)
+#endif
 #define EMU_KINDS(X, ...)                                                                                                           \
-    X(0, CT64, 1, 0, 1, 0, double, 64, __VA_ARGS__) X(1, CG64, 2, 2, 4, 4, double, 64, __VA_ARGS__)                                  \
-    X(2, CT32, 1, 0, 1, 0, float, 64, __VA_ARGS__) X(3, CG32, 2, 2, 4, 4, float, 64, __VA_ARGS__)                                    \
-    X(4, CT64n, 1, 0, 1, 0, double, 4, __VA_ARGS__) X(5, CG64n, 2, 2, 4, 4, double, 16, __VA_ARGS__)                                 \
-    X(6, CD64, 1, 1, 1, 1, double, 64, __VA_ARGS__) X(7, CD32, 1, 1, 1, 1, float, 64, __VA_ARGS__)                                   \
-    X(8, CD64n, 1, 1, 1, 1, double, 4, __VA_ARGS__)                                                                                  \
-    X(9, CX64, 2, 1, 2, 3, double, 64, __VA_ARGS__) X(10, CX64n, 2, 1, 2, 3, double, 8, __VA_ARGS__)                                 \
-    X(11, CY64, 1, 1, 2, 1, double, 64, __VA_ARGS__) X(12, CY64n, 1, 1, 2, 1, double, 4, __VA_ARGS__)
-#define EMU_TYPEDEF(k, name, a, b, c, d, R_, v_, ...) typedef Cfg<a, b, c, d, R_, v_> name;
+    X(0, CT64, 0, 0, 1, 0, 1, 0, double, 64, __VA_ARGS__) X(1, CG64, 1, 0, 2, 2, 4, 4, double, 64, __VA_ARGS__)                     \
+    X(2, CT32, 0, 1, 1, 0, 1, 0, float, 64, __VA_ARGS__) X(3, CG32, 1, 1, 2, 2, 4, 4, float, 64, __VA_ARGS__)                       \
+    X(4, CT64n, 0, 2, 1, 0, 1, 0, double, 4, __VA_ARGS__) X(5, CG64n, 1, 2, 2, 2, 4, 4, double, 16, __VA_ARGS__)                    \
+    X(6, CD64, 2, 0, 1, 1, 1, 1, double, 64, __VA_ARGS__) X(7, CD32, 2, 1, 1, 1, 1, 1, float, 64, __VA_ARGS__)                      \
+    X(8, CD64n, 2, 2, 1, 1, 1, 1, double, 4, __VA_ARGS__) X(9, CX64, 3, 0, 2, 1, 2, 3, double, 64, __VA_ARGS__)                     \
+    X(10, CX64n, 3, 2, 2, 1, 2, 3, double, 8, __VA_ARGS__) X(11, CY64, 4, 0, 1, 1, 2, 1, double, 64, __VA_ARGS__)                   \
+    X(12, CY64n, 4, 2, 1, 1, 2, 1, double, 4, __VA_ARGS__) X(13, CW64, 5, 0, 1, 1, 4, 7, double, 64, __VA_ARGS__)                   \
+    X(14, CW64n, 5, 2, 1, 1, 4, 7, double, 16, __VA_ARGS__) X(15, CR64, 6, 0, 4, 4, 2, 2, double, 64, __VA_ARGS__)                  \
+    X(16, CR64n, 6, 2, 4, 4, 2, 2, double, 8, __VA_ARGS__) X(17, CQ64, 7, 0, 2, 2, 3, 3, double, 64, __VA_ARGS__)                   \
+    X(18, CQ64n, 7, 2, 2, 2, 3, 3, double, 8, __VA_ARGS__)                                                                          \
+    EMU_KINDS_P(X, __VA_ARGS__)
+#define EMU_TYPEDEF(k, name, p_, m_, a, b, c, d, R_, v_, ...) typedef Cfg<a, b, c, d, R_, v_> name;
 EMU_KINDS(EMU_TYPEDEF, 0)
 
 struct Handle { int kind; void *p; };
 
 // runs the statements with e = the handle's Emu<CC> *
-#define EMU_CASE(k, name, a, b, c, d, R_, v_, h, ...) case k: { auto *e = (Emu<name> *)(h)->p; typedef name CC; __VA_ARGS__; } break;
+#define EMU_CASE(k, name, p_, m_, a, b, c, d, R_, v_, h, ...) case k: { auto *e = (Emu<name> *)(h)->p; typedef name CC; __VA_ARGS__; } break;
 #define DISPATCH(h, ...) switch ((h)->kind) { EMU_KINDS(EMU_CASE, h, __VA_ARGS__) }
 
 extern "C" {
@@ -89,12 +105,18 @@ void emu_debug_scrub(int on) { g_dbg_scrub = on; }
 // primitives of the kernel source, for unit tests
 double emu_py_mod360(double a) { return py_mod<double>(a, 360.0); }
 void emu_sincos(double x, double *s, double *c) { m_sincos(x, *s, *c); }
-// preset: 0 = T, 1 = G, 2 = D ; f32: 0/1 ; f32 == 2 selects the narrow-virtual-wave fp64 build
-Handle *emu_create(int preset, int f32, double W, double H, int game_len, int game_mode, int time_limit, int auto_reset,
+// the predicate of the supported shapes as this build states it (rr_sim.hpp: shape_lanes): lanes per arena, 0 = refused
+int emu_shape_lanes(int nrh, int nrg, int nbp, int nbn) { return shape_lanes(nrh, nrg, nbp, nbn, RR_CARRY != 0); }
+// preset, mode: the columns of EMU_KINDS.  Null for a combination that is not built.
+Handle *emu_create(int preset, int mode, double W, double H, int game_len, int game_mode, int time_limit, int auto_reset,
                    uint64_t seed) {
+    int kind = -1;
+#define EMU_PICK(k, name, p_, m_, ...) if (preset == p_ && mode == m_) kind = k;
+    EMU_KINDS(EMU_PICK, 0)
+    if (kind < 0) return nullptr;
     Handle *h = new Handle;
-    h->kind = preset == 4 ? (f32 == 2 ? 12 : 11) : preset == 3 ? (f32 == 2 ? 10 : 9) : preset == 2 ? 6 + f32 : preset + 2 * f32; // presets 3, 4 = X, Y (fp64 only)
-#define EMU_ALLOC(k, name, a, b, c, d, R_, v_, ...) case k: h->p = calloc(1, sizeof(Emu<name>)); break;
+    h->kind = kind;
+#define EMU_ALLOC(k, name, p_, m_, a, b, c, d, R_, v_, ...) case k: h->p = calloc(1, sizeof(Emu<name>)); break;
     switch (h->kind) { EMU_KINDS(EMU_ALLOC, 0) }
     DISPATCH(h, fill_params(e->sp, W, H, game_len, game_mode, time_limit, auto_reset, seed); (void)sizeof(CC);
              e->prog.n = 3; e->prog.id[0] = 1; e->prog.id[1] = 2; e->prog.id[2] = 3; e->custom_prog = false;

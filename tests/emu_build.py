@@ -44,7 +44,7 @@ LIBS = {
         "emu_create", "emu_destroy", "emu_set_state", "emu_get_state", "emu_set_poses", "emu_set_scratch_rect", "emu_get_scratch_rect", "emu_step",
         "emu_step_budget", "emu_park_seed", "emu_step_thrust", "emu_observe", "emu_reset", "emu_set_program", "emu_observe_kind",
         "emu_set_goal_scoring", "emu_goal_scores", "emu_py_mod360", "emu_sincos", "emu_debug_set_substeps", "emu_debug_trace", "emu_debug_memo",
-        "emu_debug_scrub")),
+        "emu_debug_scrub", "emu_shape_lanes")),
     "hive": Lib(_emu("rr_hive_emu.cpp"), "librr_hive_emu.so", _STRICT, ("hive_emu", "hive_held_emu", "hive_commit_emu", "hive_idle_emu")),
     # the hive's flags + -fno-builtin: the rewards' distances are the reference's pow(x, 2.0) / pow(x, .5) and must stay the libm calls
     # CPython makes (g++ would fold the former to x * x), as oracle/Makefile keeps them for the oracle
@@ -96,7 +96,9 @@ def build(lib, verbose=False):
 
 
 def build_all(verbose=False):
-    return [build(lib, verbose) for lib in LIBS.values()]
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=min(len(LIBS), os.cpu_count() or 1)) as ex:  # one g++ process per library, side by side
+        return list(ex.map(lambda lib: build(lib, verbose), LIBS.values()))
 
 
 def build_program(lib, path, extra=()):
@@ -116,7 +118,7 @@ def load(lib):
 
 # ---- what the bindings share
 # the emulations' preset ids; the non-square ids run their shape's build at their own W, H
-PRESET_ID = {"T": 0, "G": 1, "D": 2, "X": 3, "Y": 4}
+PRESET_ID = {"T": 0, "G": 1, "D": 2, "X": 3, "Y": 4, "W": 5, "R": 6, "Q": 7, "P": 8}
 PRESET_ID.update({wide: PRESET_ID[shape] for wide, shape in ol.SHAPE.items()})
 
 

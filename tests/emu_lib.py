@@ -53,6 +53,7 @@ def _bind(L):
     L.emu_py_mod360.restype = C.c_double
     L.emu_py_mod360.argtypes = [C.c_double]
     L.emu_sincos.argtypes = [C.c_double, dp, dp]
+    L.emu_shape_lanes.argtypes = [C.c_int] * 4
     return L
 
 
@@ -70,9 +71,10 @@ class EmuEnv:
         cfg = ol.PRESETS[preset]
         self.cfg = cfg
         _, self.nr, _, self.nb = eb.counts(preset)
-        # narrow=True: fp64 with VW = 4 (T, D) / 16 (G) lanes per arena, i.e. multi-round phases as in the packed builds
+        # narrow=True: fp64 with VW = 4 (T, D, Y, P) / 8 (X, R, Q) / 16 (G, W) lanes per arena, i.e. multi-round phases as in the packed builds
         self.h = lib(self._exact).emu_create(eb.PRESET_ID[preset], 2 if narrow else int(f32), cfg["W"], cfg["H"], cfg["game_len"],
                                              cfg["game_mode"], time_limit, int(auto_reset) | (int(reset_on_fault) << 1), seed)
+        assert self.h, f"the emulation has no build of preset {preset} (f32={f32}, narrow={narrow}, exact={self._exact})"
 
     def __del__(self):
         if getattr(self, "h", None):

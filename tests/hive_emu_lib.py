@@ -8,8 +8,8 @@ import emu_build as eb
 import oracle_lib as ol
 
 # lanes per arena the tests run the emulation at (rows of EMU_HIVE_TABLE, tests/emu/emu_common.hpp): the product's width of the shape
-# (csrc/rr_kstep.hpp; X: build.shape_lanes), wider groups and 64
-LANES = {"T": (2, 4, 64), "G": (8, 16, 32, 64), "D": (4, 64), "X": (8, 64)}
+# (csrc/rr_kstep.hpp; X, W, R: build.shape_lanes), wider groups and 64
+LANES = {"T": (2, 4, 64), "G": (8, 16, 32, 64), "D": (4, 64), "X": (8, 64), "W": (16, 64), "R": (8, 64)}
 LANES.update({wide: LANES[shape] for wide, shape in ol.SHAPE.items()})  # the non-square ids run their shape's build at their own W, H
 
 

@@ -19,6 +19,17 @@ PRESETS = {  # RR_Constants.py:6-7,24-25,30-34
     # a shape outside the library's built list (compiled on demand: roborugby_amd.build.build_shape_library): odd counts, unequal teams
     "X": dict(nr_h=2, nr_g=1, nb_p=2, nb_n=3, W=800.0, H=800.0, game_len=4500, game_mode=1),
     "Y": dict(nr_h=1, nr_g=1, nb_p=2, nb_n=1, W=800.0, H=800.0, game_len=4500, game_mode=1),  # four lanes per arena, three balls (emulation vs oracle only)
+    # the shapes at the limits of the one-shape library (roborugby_amd.build.shape_lanes; csrc/rr_sim.hpp: shape_lanes), G's constants:
+    #   W: 16 lanes per arena, 11 balls, 55 ball pairs (the upper half of the 64-bit ball-pair mask), the one-pass two-team observation
+    #   R: 8 robots, 28 robot pairs, exactly 32 ball-robot pairs (bit 31 of that mask is a real pair)
+    #   Q: 6 NR == 4 NB and NB == 6, the aliasing bound of the one-pass two-team observation at equality (emulation vs oracle only)
+    #   P: one robot with several balls, NBP (1 + NR) == 6 NR, the reward scratch's bound at equality (emulation vs oracle only; the
+    #      parity build refuses it)
+    # W and R are pinned to reference vectors (tests/golden/{traj,reset}_{W,R}.npz) and built for the GPU by __graft_entry__.build()
+    "W": dict(nr_h=1, nr_g=1, nb_p=4, nb_n=7, W=800.0, H=800.0, game_len=4500, game_mode=1),
+    "R": dict(nr_h=4, nr_g=4, nb_p=2, nb_n=2, W=800.0, H=800.0, game_len=4500, game_mode=1),
+    "Q": dict(nr_h=2, nr_g=2, nb_p=3, nb_n=3, W=800.0, H=800.0, game_len=4500, game_mode=1),
+    "P": dict(nr_h=1, nr_g=0, nb_p=3, nb_n=0, W=800.0, H=800.0, game_len=4500, game_mode=1),
     # non-square arenas: every other preset has W == H, where swapping the two anywhere changes nothing.  Dwide and Ttall are pinned to
     # reference vectors (tests/golden/{traj,reset}_{Dwide,Ttall}.npz, mix_Dwide.npz: the reference with its two arena constants patched,
     # oracle/refgen/load_reference.py); Gwide (G's counts) is for oracle-vs-emulation-vs-kernel comparisons only
@@ -26,14 +37,19 @@ PRESETS = {  # RR_Constants.py:6-7,24-25,30-34
     "Ttall": dict(nr_h=1, nr_g=0, nb_p=1, nb_n=0, W=480.0, H=720.0, game_len=300, game_mode=0),
     "Gwide": dict(nr_h=2, nr_g=2, nb_p=4, nb_n=4, W=1000.0, H=640.0, game_len=4500, game_mode=1),
 }
+LIMIT_SHAPES = ("W", "R", "Q", "P")  # no entry in the product's PRESETS: product_preset makes a custom_preset of their counts
 SHAPE = {"Dwide": "D", "Ttall": "T", "Gwide": "G"}  # the preset whose entity counts (= compiled shape) a non-square id has
 
 
 def product_preset(name):
-    """The product-side Preset of an id of PRESETS: the library's own for the square ones, its shape's with the arena size replaced for
+    """The product-side Preset of an id of PRESETS: the library's own for the square ones, a custom_preset for the limit shapes, its shape's with the arena size replaced for
     the non-square ones (roborugby_amd.config keeps no entry for them)."""
     import dataclasses
     import roborugby_amd as rr
+    if name in LIMIT_SHAPES:
+        c = PRESETS[name]
+        from roborugby_amd.config import custom_preset
+        return custom_preset(c["nr_h"], c["nr_g"], c["nb_p"], c["nb_n"], name=name)
     if name not in SHAPE:
         return rr.PRESETS[name]
     return dataclasses.replace(rr.PRESETS[SHAPE[name]], name=name, arena_w=PRESETS[name]["W"], arena_h=PRESETS[name]["H"])

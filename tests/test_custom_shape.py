@@ -16,10 +16,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def test_shape_limits_and_lane_widths():
     from roborugby_amd import build
     assert build.shape_lanes(2, 1, 2, 3) == 8 and build.shape_lanes(1, 0, 1, 0) == 2 and build.shape_lanes(2, 2, 4, 4) == 8
-    assert build.shape_lanes(1, 1, 2, 1) == 4 and build.shape_lanes(4, 4, 2, 2) == 8 and build.shape_lanes(2, 0, 6, 5) == 16
-    for bad in ((0, 1, 1, 1), (1, 0, 0, 1), (5, 4, 1, 1), (2, 2, 6, 6), (3, 3, 3, 3)):  # no happy robot / no positive ball / > 8 robots / > 11 balls / > 32 pairs
+    assert build.shape_lanes(1, 1, 2, 1) == 4 and build.shape_lanes(4, 4, 2, 2) == 8 and build.shape_lanes(1, 1, 4, 7) == 16
+    # no happy robot / no positive ball / > 8 robots / > 11 balls / > 32 pairs / more positive balls than the reward scratch holds (two)
+    for bad in ((0, 1, 1, 1), (1, 0, 0, 1), (5, 4, 1, 1), (2, 2, 6, 6), (3, 3, 3, 3), (2, 0, 6, 5), (1, 0, 4, 0)):
         with pytest.raises(ValueError):
             build.shape_lanes(*bad)
+    with pytest.raises(ValueError):  # the parity build: one robot, one ball
+        build.shape_lanes(1, 0, 2, 0, exact=True)
+    assert build.shape_lanes(1, 0, 2, 0) == 2
     assert (2, 2, 4, 4) in build.BUILT_SHAPES and (2, 1, 2, 3) not in build.BUILT_SHAPES
 
 

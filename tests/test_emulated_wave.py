@@ -17,7 +17,8 @@ def _diff(st, ref_r, ref_b):
 
 
 @pytest.mark.parametrize("preset,stride,narrow", [("T", 3, False), ("G", 4, False), ("T", 4, True), ("G", 5, True), ("D", 3, False), ("D", 4, True),
-                                                       ("X", 5, False), ("X", 6, True)])
+                                                       ("X", 5, False), ("X", 6, True),
+                                                       ("W", 3, False), ("W", 3, True), ("R", 3, False), ("R", 3, True)])
 def test_emulated_kernel_vs_reference_golden(golden_dir, preset, stride, narrow):
     """narrow=True runs the phases with VW = 4 (T) / 16 (G) lanes per arena, i.e. in several rounds -- the
     lane->task maps of the packed GPU builds (several arenas per wavefront)."""
@@ -69,7 +70,7 @@ def test_emulated_kernel_thrust_entry_vs_reference_golden(golden_dir, preset):
     print(f"[{preset}] {n} golden thrust steps through the emulated wave, worst {worst:.2e}")
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "Dwide", "Ttall", "Gwide"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "Dwide", "Ttall", "Gwide", "W", "R", "Q", "P"])
 def test_emulated_reset_equals_oracle_reset(preset):
     for arena in (0, 5, 123456789):
         e, o = el.EmuEnv(preset, seed=42), ol.OracleEnv(preset)

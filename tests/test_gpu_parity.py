@@ -35,11 +35,13 @@ def _flatten_golden(t):
 
 
 @pytest.mark.parametrize("preset,exact", [(p, e) for p in ("T", "G", "D") for e in (False, True)] + [("X", False)]
-                         + [("Dwide", False), ("Dwide", True), ("Ttall", False)],
+                         + [("Dwide", False), ("Dwide", True), ("Ttall", False)] + [("W", False), ("R", False)],
                          ids=lambda v: {False: "default", True: "exact_trig"}.get(v, v) if isinstance(v, bool) else v)
 def test_step_matches_reference_golden_f64(golden_dir, preset, exact):
     """exact=True: the same bar for the exact-trig parity build (libroborugby_amd_exact.so).  Preset X (2 + 1 robots, 2 + 3 balls) is not
     one of the shapes inside the library: it runs through the one-shape library compiled on demand (build.build_shape_library).
+    W (1 + 1 robots, 4 + 7 balls: 16 lanes per arena, 55 ball pairs) and R (4 + 4 robots, 2 + 2 balls: 8 robots, 32 ball-robot pairs) are the
+    limits of such a library (build.shape_lanes), built by __graft_entry__.build().
     Dwide (1000 x 640) and Ttall (480 x 720) are the non-square arenas: every step that tells width from height -- walls, clamps, the
     ball / wall bounce with the reference's width-for-height line, lidar, goal corner, reward multiplier -- at W != H."""
     t = np.load(f"{golden_dir}/traj_{preset}.npz")
@@ -126,7 +128,7 @@ def test_thrust_entry_matches_reference_golden(golden_dir, preset):
     print(f"[{preset}] {len(idx)} golden thrust steps replayed on GPU, worst abs state diff {worst:.3e}")
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall", "Gwide"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall", "Gwide", "W", "R"])
 def test_reset_matches_oracle_bit_exact(preset):
     """Same Philox stream + same rejection rule -> identical placements and first observations."""
     n, seed = 257, 1234
@@ -146,7 +148,7 @@ def test_reset_matches_oracle_bit_exact(preset):
     assert (st["step"] == 0).all()
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall", "W", "R"])
 def test_kernel_reset_distribution_matches_reference(golden_dir, preset):
     """The in-kernel reset (reset_arena, Philox) against the 1,000 layouts the imported reference's
     _set_random_positions produced (RR_EnvBase.py:155-200; tests/golden/reset_*.npz): 131,072 arenas constructed and

@@ -65,7 +65,8 @@ _random_layouts = he.random_layouts
 
 
 @pytest.mark.parametrize("preset,vw,mask,n", [("G", 8, 0b0011, 6000), ("G", 8, 0b1111, 3000), ("G", 64, 0b1010, 1000), ("G", 16, 0b0100, 500),
-                                              ("X", 8, 0b111, 1500), ("X", 64, 0b011, 500), ("D", 4, 0b11, 500), ("T", 2, 0b1, 500)])
+                                              ("X", 8, 0b111, 1500), ("X", 64, 0b011, 500), ("D", 4, 0b11, 500), ("T", 2, 0b1, 500),
+                                              ("W", 16, 0b11, 1500), ("W", 64, 0b01, 500), ("R", 8, 0xFF, 1500), ("R", 64, 0b10100101, 500)])
 def test_assignment_equals_the_numpy_restatement_on_random_layouts(preset, vw, mask, n):
     cfg = ol.PRESETS[preset]
     nr, nb = cfg["nr_h"] + cfg["nr_g"], cfg["nb_p"] + cfg["nb_n"]

@@ -66,9 +66,10 @@ def _drive(env, t, ep, s):
     return env.step(acts[acts >= 0])
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "Dwide", "Ttall", "W", "R"])
 def test_trajectories_bit_exact(golden_dir, preset):
-    """Dwide / Ttall: the non-square arenas (1000 x 640, 480 x 720), where a swapped width and height anywhere in the step shows."""
+    """Dwide / Ttall: the non-square arenas (1000 x 640, 480 x 720), where a swapped width and height anywhere in the step shows.
+    W / R: the limits of the one-shape library (11 balls; 8 robots, 32 ball-robot pairs), the reference's four entity counts patched."""
     t = np.load(f"{golden_dir}/traj_{preset}.npz")
     total = 0
     for ep in range(t["length"].shape[0]):
@@ -80,7 +81,7 @@ def test_trajectories_bit_exact(golden_dir, preset):
         assert cov[k] > 0, k
     if preset == "Dwide":
         assert cov["robot_collision"] > 0
-    if preset in ("G", "X"):
+    if preset in ("G", "X", "W", "R"):
         assert cov["bounce_balls"] > 0 and cov["robot_collision"] > 0
 
 
@@ -100,7 +101,7 @@ def test_thrust_entry_bit_exact(golden_dir, preset):
     assert cov["apply_force_to_ball"] > 0 and cov["bounce_ball_off_bot"] > 0 and cov["bounce_ball_off_wall"] > 0
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D", "X"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "X", "W", "R", "Q", "P"])
 def test_done_flag_is_step_counter(golden_dir, preset):
     """done = lngStepCount > GAME_LENGTH_STEPS (RR_EnvBase.py:555-559); stepping after done is flagged."""
     cfg = ol.PRESETS[preset]

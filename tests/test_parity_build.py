@@ -7,8 +7,9 @@ fl(c_old + fl(x - c_old)): state carried from pair to pair, sweep to sweep, step
 the ball; the parity build reproduces the carry (rr_sim.hpp "scratch-rect carry"; the golden trajectories dump the rect's centre as
 `state_inner`, rr_set_scratch_rect seeds it).  With both, what is left between a free-running episode and the reference is the
 reference's libm: glibc's sin / cos / pow are < 1 ulp but not always the nearest double.  Asserted here:
-  * against the golden episodes (glibc): whole episodes bit for bit -- T 14 of 16, G 12 of 15, D 9 of 11 (default build: 4 / 2 / 1);
-  * against the oracle evaluated with a correctly rounded libm (rro_debug_attribution(4)): ALL 42 episodes bit for bit to their end;
+  * against the golden episodes (glibc): whole episodes bit for bit -- T 14 of 16, G 12 of 15, D 9 of 11 (default build: 4 / 2 / 1),
+    and on the limit shapes W 10 of 11, R 8 of 11 (default build: 1 / 1);
+  * against the oracle evaluated with a correctly rounded libm (rro_debug_attribution(4)): ALL 42 + 11 episodes (W) bit for bit to their end;
   * on stuck arenas -- frozen islands, fixed points, thaws: where the carry has to survive the shortcuts -- the same oracle, bit for
     bit, with the shortcuts firing; and the shortcut-equivalence suites re-run against the parity build."""
 import os
@@ -39,7 +40,7 @@ def _full_episodes(golden_dir, preset):
     return t, np.nonzero(na_used == na_used.max())[0], int(na_used.max())
 
 
-@pytest.mark.parametrize("preset,want", [("T", (4, 14)), ("G", (2, 12)), ("D", (1, 9))])
+@pytest.mark.parametrize("preset,want", [("T", (4, 14)), ("G", (2, 12)), ("D", (1, 9)), ("W", (1, 10)), ("R", (1, 8))])
 def test_parity_build_follows_whole_golden_episodes_bit_for_bit(golden_dir, preset, want):
     t, full, na = _full_episodes(golden_dir, preset)
     fast = [ad.free_run(lambda: el.EmuEnv(preset, exact=False), t, ep, na) for ep in full]
@@ -47,13 +48,16 @@ def test_parity_build_follows_whole_golden_episodes_bit_for_bit(golden_dir, pres
     n_fast, n_exact = sum(x is None for x in fast), sum(x is None for x in exact)
     print(f"[{preset}] free-running golden episodes bit-identical to the reference to their last step: default build {n_fast}, parity build "
           f"{n_exact} of {len(full)}; first departures (parity build): {[x for x in exact if x is not None]}")
-    assert (n_fast, n_exact) == want  # the counts of round 3, on the emulation and on the MI355X alike: exact
+    assert (n_fast, n_exact) == want  # the counts of round 3, on the emulation and on the MI355X alike (W, R: the emulation's, when the limit shapes were pinned): exact
 
 
-@pytest.mark.parametrize("preset", ["T", "G", "D"])
+@pytest.mark.parametrize("preset", ["T", "G", "D", "W"])
 def test_parity_build_equals_the_reference_arithmetic_under_a_correctly_rounded_libm(golden_dir, preset):
     """every free-running golden episode, parity build and oracle side by side from the reference's step-0 state (scratch rect
-    included), the oracle's sin / cos / pow correctly rounded: bit-identical state after every step of every episode"""
+    included), the oracle's sin / cos / pow correctly rounded: bit-identical state after every step of every episode.
+    (R, 8 robots turning in steps of 0.6 degrees, is not in the list: 10 of its 11 episodes stay bit for bit, episode 9 leaves at step
+    116 because sin(5.5815629478777815) is one of the ~1 in 10^4 arguments the double-double routine does not round correctly --
+    -0.6454576877240151 for -0.645457687724015, tests/test_exact_trig.py's bound -- and the robot's y moves by one ulp.)"""
     t, full, na = _full_episodes(golden_dir, preset)
     steps = 0
     for ep in full:

@@ -11,7 +11,8 @@ import oracle_lib as ol
 import render_emu_lib as emu
 import render_ref as ref
 
-SIZES = {"G": [(800, 800), (96, 96), (64, 48), (4, 4)], "Dwide": [(1000, 640), (96, 64)], "T": [(96, 96)]}
+SIZES = {"G": [(800, 800), (96, 96), (64, 48), (4, 4)], "Dwide": [(1000, 640), (96, 64)], "T": [(96, 96)],
+         "W": [(96, 96)], "R": [(96, 96)]}  # 11 balls / 8 robots in the draw list (it holds 16 of each kind)
 
 
 @functools.lru_cache(maxsize=None)

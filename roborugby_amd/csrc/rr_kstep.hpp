@@ -98,16 +98,21 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
         asm volatile("" : "+v"(sph.W), "+v"(sph.H), "+v"(sph.rob_cdist));
         asm volatile("" : "+v"(sph.inner_h), "+v"(sph.inner_cdist));
     }
+    // The robot move's tail runs on both lanes of the robot's pair, by component (rr_sim.hpp: robot_move_comp_begin), except where that
+    // loses: the all-fp32 rows capped at 128 VGPRs by four waves per SIMD (D) spill already, and their budgeted and multi-step kernels,
+    // which carry the park state / the loop over the steps on top, spill 57 -> 96 and 78 -> 88 VGPRs with it and measured -2.9 % and
+    // -2.7 % (profiles/pair_move/).  Those keep the tail on one lane; every other row gains 1-6 %.  Same results either way.
+    constexpr bool COMP = !((MULTI || BUDGET) && sizeof(typename C::Real) == 4 && lds_waves_per_simd<C>() >= 4);
     if constexpr (!MULTI) {
         StepOut<O> o = { obs, obs_g, reward, reward_g, done, status, sp.memo ? snap : nullptr, isnap, arena,
                          (int)Arena<C>::SNAP_WORDS, (int)Arena<C>::ISNAP_WORDS };
         if constexpr (BUDGET) {
             ParkCtx pk;
             pk.buf = park + (size_t)arena * Arena<C>::PARK_WORDS; pk.budget = budget; pk.t_begin = t_begin;
-            step_arena<C, O, true>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (size_t)arena * na : nullptr,
+            step_arena<C, O, true, COMP>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (size_t)arena * na : nullptr,
                                    thrust ? thrust + (size_t)arena * 2 * na : nullptr, na, o, pk);
         } else {
-            step_arena<C, O>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (size_t)arena * na : nullptr,
+            step_arena<C, O, false, COMP>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (size_t)arena * na : nullptr,
                              thrust ? thrust + (size_t)arena * 2 * na : nullptr, na, o);
         }
     } else {
@@ -120,7 +125,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, lds_waves_per_simd<C>()) void
                              status ? status + so : nullptr, sp.memo ? snap : nullptr, isnap, arena,
                              (int)Arena<C>::SNAP_WORDS, (int)Arena<C>::ISNAP_WORDS };
             const size_t ao = repeat ? 0 : so;
-            step_arena<C, O>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (ao + (size_t)arena) * na : nullptr,
+            step_arena<C, O, false, COMP>(A, sph, sp.arena_offset + (uint64_t)arena, actions ? actions + (ao + (size_t)arena) * na : nullptr,
                              thrust ? thrust + (ao + (size_t)arena) * 2 * na : nullptr, na, o);
         }
     }

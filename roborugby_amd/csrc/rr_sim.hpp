@@ -758,6 +758,108 @@ template <class C> RR_HD void robot_move_lane(Arena<C> &A, const SimParams<typen
     corner_from_sc<R>(m.nrot, s2, c2, (R)10, (R)-20, sp.rob_cdist, trx, try_);
     robot_move_finish(A, sp, r, m, s1, c1, s3, c3, tlx, tly, trx, try_);
 }
+// ---- the same move with its tail split over the robot's lane pair BY COMPONENT (substep_phase1, PAIRED).  Nothing after the trigonometry
+// mixes x and y: fr_move and the six setters touch (cx, l, r) or (cy, t, b), the wall test is two x tests or two y tests, the clamp two x
+// arms and two y arms, fr_edges_from_rel a min / max over the x offsets and one over the y offsets.  So the even lane carries the x
+// component and the odd lane the y component of the FloatRect, and each runs robot_move_finish's operations on its own fields, in the
+// same order.  A setter of the OTHER component is fr_move's addition of 0.0 on this lane (frc_move below).
+template <typename R> struct FRC { R c, lo, hi, rot; R rel[4]; }; // centre, low edge (l | t), high edge (r | b); this component of TL TR BL BR
+template <class C> RR_HD FRC<typename C::Real> load_robot_comp(const Arena<C> &A, int r, int part) {
+    using R = typename C::Real;
+    using P = typename ArenaBody<C>::P;
+    static_assert(offsetof(P, rcy) == offsetof(P, rcx) + C::NR * sizeof(R), "rcx, rcy back to back");
+    static_assert(offsetof(P, rt) == offsetof(P, rl) + 2 * C::NR * sizeof(R) && offsetof(P, rb) == offsetof(P, rrt) + 2 * C::NR * sizeof(R), "rl rrt rt rb");
+    FRC<R> f;
+    f.c = (&A.p.rcx[0])[part * C::NR + r]; f.lo = (&A.p.rl[0])[part * 2 * C::NR + r]; f.hi = (&A.p.rrt[0])[part * 2 * C::NR + r];
+    f.rot = A.p.rrot[r];
+    for (int k = 0; k < 4; k++) f.rel[k] = A.rel[r][2 * k + part];
+    return f;
+}
+template <class C> RR_HD void store_robot_comp(Arena<C> &A, int r, int part, const FRC<typename C::Real> &f) { // (rrot, sides_ok: one lane, the caller)
+    (&A.p.rcx[0])[part * C::NR + r] = f.c; (&A.p.rl[0])[part * 2 * C::NR + r] = f.lo; (&A.p.rrt[0])[part * 2 * C::NR + r] = f.hi;
+    for (int k = 0; k < 4; k++) A.rel[r][2 * k + part] = f.rel[k];
+}
+// A setter pair of the reference -- set_left + set_top, or set_cx + set_cy: component x first, then y -- moves a lane's fields by the
+// setter's difference for its own component and by fr_move's 0.0 for the other one: x lane [d, +0.0], y lane [+0.0, d].  As ONE stream
+// that is [za, d, zb] with za = -0.0 | +0.0 and zb = +0.0 | -0.0: x + (-0.0) is x for every x, bit for bit, so the -0.0 is no operation of
+// the reference's left out or added, and the +0.0 is the reference's own (it turns a -0.0 field into +0.0).
+template <typename R> RR_HD void frc_move(FRC<R> &f, R d) { f.c += d; f.lo += d; f.hi += d; }
+template <typename R> RR_HD R frc_zero_before(int part) { return part ? (R)0 : -(R)0; }
+template <typename R> RR_HD R frc_zero_after(int part) { return part ? -(R)0 : (R)0; }
+// one setter alone (the clamp's arms), component q = 0 | 1: fr_move by d on the lane that holds it, by 0.0 on the other lane
+template <typename R> RR_HD void frc_set(FRC<R> &f, int part, int q, R d) { frc_move<R>(f, (part == q) ? d : (R)0); }
+template <typename R> RR_HD void frc_edges_from_rel(FRC<R> &f) { // fr_edges_from_rel: TL, TR, BL, BR in its order
+    const R mn = m_min(m_min(f.rel[0], f.rel[1]), m_min(f.rel[2], f.rel[3])), mx = m_max(m_max(f.rel[0], f.rel[1]), m_max(f.rel[2], f.rel[3]));
+    f.lo = mn + f.c; f.hi = mx + f.c;
+}
+template <typename R> RR_HD bool frc_hit_wall(const FRC<R> &f, const SimParams<R> &sp, int part) { // this lane's two of rob_hit_wall's four tests
+    return part ? (f.lo <= (R)0 || f.hi >= sp.H) : (f.lo < (R)0 || f.hi > sp.W);
+}
+// rob_clamp's arm a (0 left, 1 right, 2 top, 3 bottom): its test, on the lane that holds component a >> 1, and its setter, on both
+template <typename R> RR_HD bool frc_clamp_test(const FRC<R> &f, const SimParams<R> &sp, int a) {
+    return a == 0 ? f.lo < (R)0 : a == 1 ? f.hi > sp.W : a == 2 ? f.lo <= (R)0 : f.hi >= sp.H;
+}
+template <typename R> RR_HD void frc_clamp_arm(FRC<R> &f, const SimParams<R> &sp, int part, int a) {
+    const R buffer = (R).5;
+    const R v = (a & 1) ? (a == 1 ? sp.W : sp.H) - buffer : buffer;
+    frc_set<R>(f, part, a >> 1, v - ((a & 1) ? f.hi : f.lo));
+}
+// robot_move_finish up to the wall test, on one lane of the pair: k1 = c1 | s1, k3 = c3 | s3, tl / tr = this component of the new TL / TR
+// corner offsets.  Returns this lane's half of `blocked`.
+template <class C>
+RR_HD bool robot_move_comp_begin(const Arena<C> &A, const SimParams<typename C::Real> &sp, int r, int part, const MovePlan<typename C::Real> &m,
+                                 typename C::Real k1, typename C::Real k3, typename C::Real tl, typename C::Real tr,
+                                 FRC<typename C::Real> &f, typename C::Real &pc, typename C::Real &rot_prior) {
+    using R = typename C::Real;
+    f = load_robot_comp(A, r, part);
+    rot_prior = f.rot; pc = f.c;
+    if (m.lin) {
+        // c1 * vel | s1 * vel * -1 = s1 * (-vel): a product's sign is the XOR of its factors' signs and nothing else of it depends on them
+        const R k = k1 * (((m.L < 0) != (part != 0)) ? (R)-1 : (R)1);
+        frc_move<R>(f, frc_zero_before<R>(part));
+        frc_move<R>(f, (f.lo + k) - f.lo); // set_left(l + ..) | set_top(t + ..)
+        frc_move<R>(f, frc_zero_after<R>(part));
+    } else {
+        if (m.nrot != f.rot) {
+            f.rot = m.nrot;
+            f.rel[0] = tl; f.rel[1] = tr; f.rel[2] = -tr; f.rel[3] = -tl; // BL = -TR, BR = -TL
+            frc_edges_from_rel<R>(f);
+        }
+        if (!m.spin) {
+            // cpx = px + 16 c1, px' = cpx + 16 c3 | cpy = py - 16 s1, py' = cpy - 16 s3: a - 16 s is a + (-16) s (a - b IS a + (-b), and the
+            // sign of a product as above)
+            const R k16 = part ? (R)-16 : (R)16;
+            const R cp = pc + k16 * k1, v = cp + k16 * k3;
+            frc_move<R>(f, frc_zero_before<R>(part));
+            frc_move<R>(f, v - f.c); // set_cx | set_cy
+            frc_move<R>(f, frc_zero_after<R>(part));
+        }
+    }
+    return frc_hit_wall<R>(f, sp, part);
+}
+// ... and its `if (blocked)` arm, once the two halves are OR-ed: centre back, and after a turn the rotation setter on (rot_prior + 720) % 360
+template <class C>
+RR_HD void robot_move_comp_revert(const Arena<C> &A, const SimParams<typename C::Real> &sp, int r, int part, const MovePlan<typename C::Real> &m,
+                                  FRC<typename C::Real> &f, typename C::Real pc, typename C::Real rot_prior) {
+    using R = typename C::Real;
+    frc_move<R>(f, frc_zero_before<R>(part));
+    frc_move<R>(f, pc - f.c); // set_cx(px) | set_cy(py)
+    frc_move<R>(f, frc_zero_after<R>(part));
+    if (!m.lin) {
+        const R nr = norm360<R>(rot_prior); // (see robot_move_finish: almost always rot_prior itself, and then the corners are the ones in LDS)
+        if (nr != f.rot) {
+            f.rot = nr;
+            if (nr == rot_prior) {
+                for (int k = 0; k < 4; k++) f.rel[k] = A.rel[r][2 * k + part];
+            } else { // the rare arm: both lanes build all eight offsets and keep their component
+                R rel[8];
+                corners_for<R>(nr, (R)10, (R)20, sp.rob_cdist, rel);
+                for (int k = 0; k < 4; k++) f.rel[k] = part ? rel[2 * k + 1] : rel[2 * k];
+            }
+            frc_edges_from_rel<R>(f);
+        }
+    }
+}
 // Robot.undo_move (RR_Robot.py:110-137): back to the pose stored at frame begin
 template <class C> RR_HD void robot_undo_lane(Arena<C> &A, const SimParams<typename C::Real> &sp, int r) {
     using R = typename C::Real;
@@ -2229,18 +2331,19 @@ RR_HD void undo_naughty_movement(Arena<C> &A, const SimParams<typename C::Real> 
 }
 
 // the two fast phases of a sub-step (see substep); FZ: an island is frozen
-template <class C, bool FZ>
+template <class C, bool FZ, bool COMP = true>
 RR_HD void substep_phase1(Arena<C> &A, const SimParams<typename C::Real> &sp, const Hit &fz, uint32_t prev_moved, uint64_t &m_rr,
                           uint64_t &m_br, uint64_t &m_wm, uint64_t &m_brk) {
     using R = typename C::Real;
     // A robot's move is spread over a PAIR of lanes (2r, 2r+1) when the virtual wave has them: both lanes run the same
     // instructions on different data -- two of the three sin/cos evaluations at once, then one renormalised corner each --
-    // and swap results through DPP.  Same operations on the same operands as robot_move_lane; ~30 % fewer instructions.
+    // and swap results through DPP; the move's tail then runs on both lanes by component, x on the even lane and y on the odd one
+    // (robot_move_comp_begin).  Same operations on the same operands in the same order as robot_move_lane.
     constexpr bool PAIRED = C::VW >= 2 * C::NR;
     RR_LANE_VAR(R, sv); RR_LANE_VAR(R, cv); // sin / cos of this lane's angle: a1 on the even lane, a2 on the odd one
-    RR_LANE_VAR(R, qx); RR_LANE_VAR(R, qy); // this lane's corner: TL on the even lane, TR on the odd one
+    RR_LANE_VAR(R, qx); RR_LANE_VAR(R, qy); // this lane's corner (TL on the even lane, TR on the odd one): the lane's own component, the partner's
     RR_LANE_VAR(MovePlan<R>, mp);           // the robot's move plan (both lanes of the pair hold a copy)
-    RR_LANE_VAR(R, s3v); RR_LANE_VAR(R, c3v); // sin / cos of the third angle (the re-centring after a pivot), issued with the corners
+    RR_LANE_VAR(R, k1v); RR_LANE_VAR(R, k3v); // this lane's component of the first and the third angle (the re-centring after a pivot): cos | sin
     RR_FOR_LANES(l) {
         bool c_rr = false, c_br = false, c_brk = false; // (c_brk, frozen variant: an outside ball within the bound of an ISLAND robot -- see "witness" in substep)
         const int r = PAIRED ? (l >> 1) : l, part = PAIRED ? (l & 1) : 0;
@@ -2321,13 +2424,86 @@ RR_HD void substep_phase1(Arena<C> &A, const SimParams<typename C::Real> &sp, co
             if (r < C::NR) {
                 corner_from_sc<R>(RR_LV(mp, l).nrot, s2, c2, part ? (R)10 : (R)-10, (R)-20, sp.rob_cdist, ax, ay);
             }
-            RR_LV(qx, l) = ax; RR_LV(qy, l) = ay;
-            // the third angle's sin/cos does not depend on the corners: issued here, next to them (same instructions for the wave,
-            // only the even lane's values are used), the two chains overlap instead of running one after the other (G +1.5 %)
+            // from here on the even lane carries the move's x component and the odd lane its y component (robot_move_comp_begin): the
+            // lane keeps its component of its own corner and offers the other one to its partner
+            if constexpr (COMP) {
+                RR_LV(qx, l) = part ? ay : ax; RR_LV(qy, l) = part ? ax : ay;
+                RR_LV(k1v, l) = part ? ps : RR_LV(cv, l); // c1 | s1: a1's sin/cos sits in the even lane
+            } else { // (the one-lane tail below: the corner as (x, y))
+                RR_LV(qx, l) = ax; RR_LV(qy, l) = ay;
+            }
+            // the third angle's sin/cos does not depend on the corners: issued here, next to them (same instructions for the wave),
+            // the two chains overlap instead of running one after the other (G +1.5 %)
             R s3_ = (R)0, c3_ = (R)1;
             if (r < C::NR) sincos_deg<R>(RR_LV(mp, l).a3, s3_, c3_);
-            RR_LV(s3v, l) = s3_; RR_LV(c3v, l) = c3_;
+            if constexpr (COMP) { RR_LV(k3v, l) = part ? s3_ : c3_; }
+            else { RR_LV(k1v, l) = s3_; RR_LV(k3v, l) = c3_; } // (the one-lane tail: sin and cos of the third angle)
         }
+        if constexpr (COMP) {
+        RR_LANE_VAR(FRC<R>, fc); RR_LANE_VAR(R, pcv); RR_LANE_VAR(R, rpv); // the lane's component rect; its centre and the rotation before the move
+        RR_LANE_VAR(int, hv);  // this lane's half of `blocked`
+        RR_LANE_VAR(int, wmv); // what goes to A.wm (both lanes of the pair hold it)
+        RR_LANE_VAR(int, cav); // the clamp's exact path: 1 = the pair takes it, 2 = the arm at hand fires on this lane's component
+        RR_FOR_LANES(l) {
+            const int r = l >> 1, part = l & 1;
+            const R qo = RR_XOR1(qy, l); // the partner's corner, this lane's component: TR on the even lane, TL on the odd one
+            bool half = false;
+            if (r < C::NR && !RR_LV(mp, l).idle) {
+                const R tl = part ? qo : RR_LV(qx, l), tr = part ? RR_LV(qx, l) : qo;
+                half = robot_move_comp_begin(A, sp, r, part, RR_LV(mp, l), RR_LV(k1v, l), RR_LV(k3v, l), tl, tr, RR_LV(fc, l), RR_LV(pcv, l), RR_LV(rpv, l));
+            }
+            RR_LV(hv, l) = half ? 1 : 0;
+        }
+        uint64_t m_cl = 0;
+        RR_FOR_LANES(l) {
+            const int r = l >> 1, part = l & 1;
+            const bool blocked = (RR_LV(hv, l) | RR_XOR1(hv, l)) != 0;
+            bool c2 = false;
+            if (r < C::NR && !RR_LV(mp, l).idle) {
+                if (blocked) robot_move_comp_revert(A, sp, r, part, RR_LV(mp, l), RR_LV(fc, l), RR_LV(pcv, l), RR_LV(rpv, l));
+                // rob_clamp: no arm fires unless one of the four tests holds on the rect as it stands (an arm's test reads what the arms
+                // before it wrote, and those wrote nothing then)
+                c2 = frc_clamp_test<R>(RR_LV(fc, l), sp, 2 * part) || frc_clamp_test<R>(RR_LV(fc, l), sp, 2 * part + 1);
+            }
+            RR_LV(wmv, l) = blocked ? 1 : 0;
+            RR_LV(cav, l) = c2 ? 1 : 0;
+            RR_VOTE(m_cl, l, c2);
+        }
+        if (RR_UNLIKELY(m_cl != 0)) { // a robot across a wall: the four arms in the reference's order, each test handed to the partner lane
+            RR_FOR_LANES(l) { RR_LV(hv, l) = RR_LV(cav, l) | RR_XOR1(cav, l); }
+            for (int a = 0; a < 4; a++) {
+                RR_FOR_LANES(l) {
+                    const int r = l >> 1, part = l & 1;
+                    const bool mine = r < C::NR && RR_LV(hv, l) && part == (a >> 1) && frc_clamp_test<R>(RR_LV(fc, l), sp, a);
+                    RR_LV(cav, l) = mine ? 2 : 0;
+                }
+                RR_FOR_LANES(l) {
+                    const int r = l >> 1, part = l & 1;
+                    const bool fire = ((RR_LV(cav, l) | RR_XOR1(cav, l)) & 2) != 0;
+                    if (r < C::NR && fire) { frc_clamp_arm<R>(RR_LV(fc, l), sp, part, a); RR_LV(wmv, l) |= 2; }
+                }
+            }
+        }
+        RR_FOR_LANES(l) {
+            const int r = l >> 1, part = l & 1;
+            bool wm_changed = false;
+            if (r < C::NR) {
+                const bool idle = RR_LV(mp, l).idle;
+                if (!idle) store_robot_comp(A, r, part, RR_LV(fc, l));
+                if (part == 0) { // what one lane writes for the robot
+                    const int wm_before = FZ ? A.wm[r] : 0;
+                    A.i.mc[r] += 1;
+                    if (!idle) { A.p.rrot[r] = RR_LV(fc, l).rot; A.sides_ok = 0; }
+                    A.wm[r] = (uint8_t)(idle ? 0 : RR_LV(wmv, l));
+                    if (FZ) wm_changed = ((fz.r >> r) & 1u) && A.wm[r] != wm_before; // the frozen robot met the walls differently
+                }
+            }
+            if (FZ) RR_VOTE(m_wm, l, wm_changed);
+        }
+        } else {
+        // COMP = false: the move's tail on the even lane alone (robot_move_finish), the odd lane idle.  Kept for the kernels in which
+        // the split costs more than it saves: the all-fp32 rows at four waves per SIMD (128 VGPRs) that also carry the budget's or the
+        // rollout's state -- k_step (rr_kstep.hpp) says which, profiles/pair_move/README.md why.  Same results, bit for bit.
         RR_FOR_LANES(l) {
             const int r = l >> 1, part = l & 1;
             const R trx = RR_XOR1(qx, l), try_ = RR_XOR1(qy, l); // the odd lane's corner (TR), seen from the even lane
@@ -2337,7 +2513,7 @@ RR_HD void substep_phase1(Arena<C> &A, const SimParams<typename C::Real> &sp, co
                 const int wm_before = FZ ? A.wm[r] : 0;
                 A.i.mc[r] += 1;
                 if (!m.idle) {
-                    const R s3 = RR_LV(s3v, l), c3 = RR_LV(c3v, l);
+                    const R s3 = RR_LV(k1v, l), c3 = RR_LV(k3v, l);
                     robot_move_finish(A, sp, r, m, RR_LV(sv, l), RR_LV(cv, l), s3, c3, RR_LV(qx, l), RR_LV(qy, l), trx, try_);
                 } else {
                     A.wm[r] = 0;
@@ -2345,6 +2521,7 @@ RR_HD void substep_phase1(Arena<C> &A, const SimParams<typename C::Real> &sp, co
                 if (FZ) wm_changed = ((fz.r >> r) & 1u) && A.wm[r] != wm_before; // the frozen robot met the walls differently
             }
             if (FZ) RR_VOTE(m_wm, l, wm_changed);
+        }
         }
     }
 }
@@ -2452,7 +2629,7 @@ template <class C> RR_HD void thaw_island(Arena<C> &A, const SimParams<typename 
 // like every robot (how it meets the walls depends on their drifting edges) and are put back at the end of the sub-step.
 // Budgeted step: returns true when the arena parked between two passes of the resolve loop (`mid` holds where); a call with
 // mid->phase == 1 skips everything before that loop and re-enters it.
-template <class C, bool BUDGET = false>
+template <class C, bool BUDGET = false, bool COMP = true>
 RR_HD bool substep(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t &naughty, int &st, uint32_t &prev_moved,
                    int &work, Hit &fz, Hit &hit, int &icm, MidState *mid = nullptr, const ParkCtx *pk = nullptr) {
     using R = typename C::Real;
@@ -2474,8 +2651,8 @@ RR_HD bool substep(Arena<C> &A, const SimParams<typename C::Real> &sp, uint32_t 
     // displacement a move can cause (1 px drive / 0.17 px pivot / <= 1.5 px wall clamp: 3 px per robot is generous).
     uint64_t m_rr = 0, m_br = 0, m_wm = 0, m_brk = 0;
     const bool frozen = (fz.r | fz.b) != 0; // the frozen variants are separate instantiations: the common path pays nothing
-    if (RR_UNLIKELY(frozen)) substep_phase1<C, true>(A, sp, fz, prev_moved, m_rr, m_br, m_wm, m_brk);
-    else substep_phase1<C, false>(A, sp, fz, prev_moved, m_rr, m_br, m_wm, m_brk);
+    if (RR_UNLIKELY(frozen)) substep_phase1<C, true, COMP>(A, sp, fz, prev_moved, m_rr, m_br, m_wm, m_brk);
+    else substep_phase1<C, false, COMP>(A, sp, fz, prev_moved, m_rr, m_br, m_wm, m_brk);
     RR_SYNC();
     RR_STAMP(1);
     // Witness (default build).  A ball OUTSIDE the island within the bounds of one of its robots -- drifting past its flank, half a
@@ -3184,7 +3361,7 @@ RR_HD void park_load(Arena<C> &A, const uint32_t *buf, int &f_next, uint32_t &pr
 }
 
 // actions: this arena's na discrete actions (thrust == nullptr) or 2*na thrust floats
-template <class C, typename O, bool BUDGET = false>
+template <class C, typename O, bool BUDGET = false, bool COMP = true>
 RR_HD void step_arena(Arena<C> &A, const SimParams<typename C::Real> &sp, uint64_t arena_gid, const int32_t *actions,
                       const float *thrust, int na, const StepOut<O> &o, const ParkCtx &pk = ParkCtx()) {
     using R = typename C::Real;
@@ -3308,7 +3485,7 @@ RR_HD void step_arena(Arena<C> &A, const SimParams<typename C::Real> &sp, uint64
         uint32_t n_sub = 0; // what THIS sub-step adds: a freeze keeps it for the frozen sub-steps of later steps
         int st_sub = 0;
         if constexpr (BUDGET) {
-            const bool parked_mid = substep<C, true>(A, sp, n_sub, st_sub, prev_moved, work, fz, hit, icm, &mid, &pk);
+            const bool parked_mid = substep<C, true, COMP>(A, sp, n_sub, st_sub, prev_moved, work, fz, hit, icm, &mid, &pk);
             if (RR_UNLIKELY(parked_mid)) {
                 RR_TRACE("E parked inside sub-step %d before resolve pass %d\n", f, mid.count + 1);
                 park_save(A, pk.buf, f, prev_moved, naughty, st, fz, fz_bits, snap_at == f - 1, snap_moved, dist_sum0, mid);
@@ -3320,7 +3497,7 @@ RR_HD void step_arena(Arena<C> &A, const SimParams<typename C::Real> &sp, uint64
                 return;
             }
         } else {
-            substep(A, sp, n_sub, st_sub, prev_moved, work, fz, hit, icm);
+            substep<C, false, COMP>(A, sp, n_sub, st_sub, prev_moved, work, fz, hit, icm);
         }
         naughty |= n_sub; st |= st_sub;
 #if defined(RR_PROFILE_PHASES) // diagnostic builds only: the step's contact work in status bits 20-29, "began frozen" in bit 30

@@ -489,6 +489,57 @@ int rr_cnn_act(rr_dqn *dqn, const float *const params[8], const uint8_t *pixels,
 int rr_sac_act(rr_dqn *dqn, const float *const params[8], const float *obs, int32_t n, int32_t n_actions, float max_action,
                int32_t flags, uint64_t seed, uint32_t call, float *actions, float *log_prob, float *head, float *noise, void *stream);
 
+/* ---- the no-grad half of the SAC agent's learn (roborugby_amd/csrc/rr_sac.hip k_sac_targets, rr_sac.hpp; roborugby_amd/sac.py
+ * BatchedSACAgent.targets): the two vectors Agent.learn (Training_SAC_pytorch.py:344-383) computes without a gradient, for B replay rows
+ * gathered out of the caller's rings, in ONE launch on the fp32 matrix cores:
+ *   value_target[b] = min(Q1, Q2)(s_b, a~_b) - log pi(a~_b | s_b)      a~ a fresh (non-reparameterised) sample of the policy at s_b
+ *   q_hat[b]        = reward_scale * r_b + gamma * (done_b ? 0 : V_target(s'_b))
+ * The backward passes stay with the caller (autograd); `state` / `action` hand it the gathered rows it still needs.
+ * Parameters in torch.nn.Linear layouts and fp32, read as they stand at call time (nothing is kept in the handle).
+ * THE ARITHMETIC (this is the specification; tests/sac_targets_ref.py is it in numpy):
+ *   Gather.  Batch row b takes ring row i = batch_index[b] (batch_index == NULL: i = b).  An i outside [0, mem_rows) is never used as an
+ *     address: every output of that batch row that was passed is NaN (its `state` / `action` rows included); other batch rows are
+ *     unaffected.
+ *   Policy sample.  rr_sac_act's arithmetic on state_memory[i]: the head in fp32 (fp32 products summed in fp32, in no particular order),
+ *     sigma = clamp(raw, 1e-6, 1), a~_k = max_action * tanhf(mu_k + sigma_k z_k), log_prob = rr_sac_act's formula with the SCALED action.
+ *     noise == NULL: z = rr_sac_act's draw (Philox4x32-10, Box-Muller) of counter (b, call, 0x5A7A, 0) under key (seed: low word, high
+ *     word) -- another stream word than rr_sac_act's 0x5AC7, so one (seed, call) never correlates acting and learning; the row word is the
+ *     BATCH POSITION b, not the ring row.  noise != NULL: z = noise[b] ([B, A]).  Pass a fresh `call` every time.
+ *   Critics.  q_j = CriticNetwork_j([s, a~]) (11 + A inputs; hidden layers as above), the single output an fp32 dot plus the fp32 bias.
+ *     value_target = fminf(q1, q2) - log_prob: one subtraction of the two fp32 numbers the windows report.
+ *   Next value.  v_next = ValueNetwork_target(new_state_memory[i]); the window reports it whether or not the row is terminal.
+ *     q_hat = reward_scale * r + gamma * (done ? 0.0f : v_next), without contraction: fl(fl(reward_scale * r) + fl(gamma * v)), on a
+ *     terminal row exactly fl(reward_scale * r).
+ * Every element of every output that was passed is written for rows < B; nothing at or beyond row B is read or written; nothing is kept
+ * in the handle; no atomics.  The results are bit-identical for any grid size (RR_DQN_WGS) and whether the draws came from the kernel or
+ * were fed back through `noise` (noise_out of an earlier call).
+ * Returns -1 (message "rr_sac_targets: ...": rr_dqn_last_error) and launches nothing for: a null handle, args or required pointer (a
+ * parameter entry, a ring, value_target, q_hat), a wrong struct_size, a batch that is not a positive multiple of 64, n_actions outside
+ * {2, 4}, mem_rows < 1, batch_index == NULL with mem_rows < batch, a max_action that is not finite and > 0, a non-finite gamma or
+ * reward_scale, non-zero flags. */
+typedef struct rr_sac_targets_args {
+    int32_t struct_size;               /* = sizeof(rr_sac_targets_args) */
+    int32_t batch;                     /* B: a positive multiple of 64 */
+    int32_t n_actions;                 /* A: 2 or 4 */
+    int32_t flags;                     /* 0 */
+    const float *actor[8];             /* rr_sac_act's order */
+    const float *critic_1[6], *critic_2[6];   /* fc1.weight [256, 11+A], fc1.bias, fc2.weight [256,256], fc2.bias, q.weight [1,256], q.bias [1] */
+    const float *target_value[6];      /* fc1.weight [256,11], fc1.bias, fc2.weight, fc2.bias, v.weight [1,256], v.bias [1] */
+    const float *state_memory, *new_state_memory;  /* [mem_rows, 11] */
+    const float *action_memory;        /* [mem_rows, A] */
+    const float *reward_memory;        /* [mem_rows] */
+    const uint8_t *terminal_memory;    /* [mem_rows] (torch.bool) */
+    int64_t mem_rows;                  /* rows of the rings that may be addressed: >= 1 */
+    const int64_t *batch_index;        /* [B] rows of the rings; NULL: rows 0 .. B-1 (then mem_rows >= B) */
+    const float *noise;                /* nullable [B, A]: the standard normal draws to use; NULL: the kernel draws */
+    float max_action, gamma, reward_scale;
+    uint64_t seed; uint32_t call;      /* key the draws when noise == NULL */
+    float *value_target, *q_hat;       /* required, [B] each */
+    float *state, *action;             /* nullable: the gathered rows [B,11], [B,A] (what the autograd half still needs) */
+    float *policy_action, *log_prob, *head, *noise_out, *q1, *q2, *v_next;  /* nullable windows: [B,A], [B], [B,2A], [B,A], [B], [B], [B] */
+} rr_sac_targets_args;
+int rr_sac_targets(rr_dqn *dqn, const rr_sac_targets_args *args, void *stream);
+
 /* ---- the frame-sharing pixel replay (roborugby_amd/csrc/rr_frames.hpp, rr_frames.hip; roborugby_amd/frame_replay.py FrameReplay): a ring
  * that stores every frame ONCE instead of two whole stacked observations per transition.  The caller owns the ring (device memory):
  *   frames  u8  [slots, rows, frame_bytes]   the newest frame of every row after push k, in slot k % slots

@@ -39,6 +39,21 @@ class RRDqnArgs(C.Structure):
     ]
 
 
+class RRSacTargetsArgs(C.Structure):
+    """rr_sac_targets_args (include/roborugby_amd.h)"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("batch", C.c_int32), ("n_actions", C.c_int32), ("flags", C.c_int32),
+        ("actor", C.c_void_p * 8), ("critic_1", C.c_void_p * 6), ("critic_2", C.c_void_p * 6), ("target_value", C.c_void_p * 6),
+        ("state_memory", C.c_void_p), ("new_state_memory", C.c_void_p), ("action_memory", C.c_void_p), ("reward_memory", C.c_void_p),
+        ("terminal_memory", C.c_void_p), ("mem_rows", C.c_int64), ("batch_index", C.c_void_p), ("noise", C.c_void_p),
+        ("max_action", C.c_float), ("gamma", C.c_float), ("reward_scale", C.c_float),
+        ("seed", C.c_uint64), ("call", C.c_uint32),
+        ("value_target", C.c_void_p), ("q_hat", C.c_void_p), ("state", C.c_void_p), ("action", C.c_void_p),
+        ("policy_action", C.c_void_p), ("log_prob", C.c_void_p), ("head", C.c_void_p), ("noise_out", C.c_void_p),
+        ("q1", C.c_void_p), ("q2", C.c_void_p), ("v_next", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/roborugby_amd.h declares
 _vp = C.c_void_p
 SYMBOLS = {
@@ -93,6 +108,7 @@ SYMBOLS = {
     "rr_dqn_act": (C.c_int, [_vp, C.POINTER(_vp * 6), _vp, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
     "rr_cnn_act": (C.c_int, [_vp, C.POINTER(_vp * 8), _vp, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
     "rr_sac_act": (C.c_int, [_vp, C.POINTER(_vp * 8), _vp, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "rr_sac_targets": (C.c_int, [_vp, C.POINTER(RRSacTargetsArgs), _vp]),
     "rr_frames_push": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rr_frames_sample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_uint64,
                                    C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -265,3 +281,30 @@ class DqnHandle(_Handle):
         ptrs = (C.c_void_p * 8)(*[p.data_ptr() for p in params])
         self.launch("rr_sac_act", C.byref(ptrs), ptr(obs), n, n_actions, float(max_action), RR_SAC_DETERMINISTIC if deterministic else 0,
                     int(seed) & 0xFFFFFFFFFFFFFFFF, calls & 0xFFFFFFFF, ptr(actions), ptr(log_prob), ptr(head), ptr(noise))
+
+    def sac_targets(self, actor, critic_1, critic_2, target_value, rings, mem_rows, batch, n_actions, max_action, gamma, reward_scale,
+                    value_target, q_hat, batch_index=None, noise=None, seed=0, calls=0, state=None, action=None, **windows):
+        """rr_sac_targets: the no-grad half of the SAC learn step in one launch.  actor (eight tensors, rr_sac_act's order), critic_1,
+        critic_2, target_value (six each); rings = (state_memory, new_state_memory, action_memory, reward_memory, terminal_memory) of
+        which rows 0 .. mem_rows-1 may be addressed; batch_index int64 [batch] (None: rows 0 .. batch-1); noise [batch, n_actions] (None:
+        the kernel draws under (seed, the low 32 bits of `calls`)).  Written: value_target, q_hat [batch]; optionally the gathered state
+        [batch, 11] / action [batch, n_actions] and the windows policy_action, log_prob, head, noise_out, q1, q2, v_next (keywords)."""
+        a = RRSacTargetsArgs()
+        a.struct_size, a.batch, a.n_actions, a.flags = C.sizeof(RRSacTargetsArgs), int(batch), int(n_actions), 0
+        for field, params in (("actor", actor), ("critic_1", critic_1), ("critic_2", critic_2), ("target_value", target_value)):
+            arr = getattr(a, field)
+            if len(params) != len(arr):
+                raise ValueError(f"sac_targets: {field} takes {len(arr)} tensors, got {len(params)}")
+            for k, p in enumerate(params):
+                arr[k] = p.data_ptr()
+        (a.state_memory, a.new_state_memory, a.action_memory, a.reward_memory, a.terminal_memory) = (t.data_ptr() for t in rings)
+        a.mem_rows = int(mem_rows)
+        a.batch_index, a.noise = ptr(batch_index), ptr(noise)
+        a.max_action, a.gamma, a.reward_scale = float(max_action), float(gamma), float(reward_scale)
+        a.seed, a.call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(calls) & 0xFFFFFFFF
+        a.value_target, a.q_hat, a.state, a.action = ptr(value_target), ptr(q_hat), ptr(state), ptr(action)
+        for k in ("policy_action", "log_prob", "head", "noise_out", "q1", "q2", "v_next"):
+            setattr(a, k, ptr(windows.pop(k, None)))
+        if windows:
+            raise TypeError(f"sac_targets: unknown windows {sorted(windows)}")
+        self.launch("rr_sac_targets", C.byref(a))

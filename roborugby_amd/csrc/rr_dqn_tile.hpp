@@ -1,6 +1,7 @@
-// rr_dqn_tile.hpp -- the two 256-wide hidden layers of the reference's MLPs (Linear 11 -> 256 -> 256, ReLU) for one 64-row tile on the
-// fp32 matrix cores, as the kernels behind the rr_dqn handle share them: rr_dqn.hip (k_dqn_fwd_bwd, k_dqn_act: the Q network) and
-// rr_sac.hip (k_sac_act: the SAC actor).  Device code only; what a tile's head does with X1 is the including kernel's business.
+// rr_dqn_tile.hpp -- the two 256-wide hidden layers of the reference's MLPs (Linear K -> 256 -> 256, ReLU; K = 11, or 11 + A for the SAC
+// critics) for one 64-row tile on the fp32 matrix cores, as the kernels behind the rr_dqn handle share them: rr_dqn.hip (k_dqn_fwd_bwd,
+// k_dqn_act: the Q network) and rr_sac.hip (k_sac_act: the SAC actor; k_sac_targets: actor, critics and target value net).  Device code
+// only; what a tile's head does with X1 is the including kernel's business.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,23 +18,23 @@ __device__ __forceinline__ f16v mfma(float a, float b, f16v c) { return __builti
 // row of a 32 x 32 accumulator tile held in register r of a lane in half `half` (lanes 32-63: half = 1); its column is lane & 31
 __device__ __forceinline__ int acc_row(int r, int half) { return 8 * (r >> 2) + 4 * half + (r & 3); }
 
-// hidden layers of one net (its members w1, b1, w2, b2: torch.nn.Linear layouts) for the tile in Sb ([12][LDX], row 11 = 0):
-// X0 = relu(fc1), X1 = relu(fc2), both transposed [feature][sample].  Every thread of the workgroup calls it (w = wavefront,
-// half = lane >> 5, c = lane & 31); it ends behind a barrier: X1 is complete for every thread.
-template <class NetT>
+// hidden layers of one net (its members w1 [256, K], b1, w2, b2: torch.nn.Linear layouts) for the tile in Sb ([K padded to even][LDX],
+// the pad row = 0; K = 11: [12][LDX], row 11 = 0): X0 = relu(fc1), X1 = relu(fc2), both transposed [feature][sample].  Every thread of the
+// workgroup calls it (w = wavefront, half = lane >> 5, c = lane & 31); it ends behind a barrier: X1 is complete for every thread.
+template <int K = IN, class NetT>
 __device__ __forceinline__ void hidden_tile(const NetT &net, const float *Sb, float *X0, float *X1, int w, int half, int c) {
     f16v acc[4];
-    // ---- fc1: K = 11 (padded to 12), output tiles: n-tiles {2w, 2w+1} x m-tiles {0, 1}
+    // ---- fc1: K inputs (11 padded to 12), output tiles: n-tiles {2w, 2w+1} x m-tiles {0, 1}
 #pragma unroll
     for (int q = 0; q < 4; q++) acc[q] = (f16v)0.0f;
 #pragma unroll
-    for (int p = 0; p < 6; p++) {
+    for (int p = 0; p < (K + 1) / 2; p++) {
         const int k = 2 * p + half;
         const float a0 = Sb[k * LDX + c], a1 = Sb[k * LDX + 32 + c];
 #pragma unroll
         for (int nt = 0; nt < 2; nt++) {
             const int n = (2 * w + nt) * 32 + c;
-            const float b = k < IN ? net.w1[n * IN + k] : 0.0f;
+            const float b = k < K ? net.w1[n * K + k] : 0.0f;
             acc[nt * 2 + 0] = mfma(a0, b, acc[nt * 2 + 0]);
             acc[nt * 2 + 1] = mfma(a1, b, acc[nt * 2 + 1]);
         }

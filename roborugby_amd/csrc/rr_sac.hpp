@@ -1,6 +1,8 @@
-// rr_sac.hpp -- the per-row arithmetic of rr_sac_act's epilogue (include/roborugby_amd.h is the specification): the standard normal
-// draws of a row, the clamp of sigma, the squashed action and a component's share of the log-probability.  Plain C++ as well as HIP:
-// tests/emu/rr_sac_emu.cpp compiles these very functions with g++ and holds them to tests/sac_ref.py without a GPU.
+// rr_sac.hpp -- the per-row arithmetic of rr_sac_act's and rr_sac_targets' epilogues (include/roborugby_amd.h is the specification): the
+// standard normal draws of a row, the clamp of sigma, the squashed action and a component's share of the log-probability; the gather's
+// bounds rule and the two closing formulas of the learn targets.  Plain C++ as well as HIP: tests/emu/rr_sac_emu.cpp and
+// tests/emu/rr_sac_targets_emu.cpp compile these very functions with g++ and hold them to tests/sac_ref.py / tests/sac_targets_ref.py
+// without a GPU.
 #pragma once
 #include <math.h>
 #include "rr_dqn_shared.hpp"
@@ -8,6 +10,7 @@
 namespace rr {
 
 constexpr uint32_t SAC_STREAM = 0x5AC7u;  // counter word 2 of the draws (rr_dqn_act / rr_cnn_act: 0x0AC7, rr_frames_sample: 0x5A3E)
+constexpr uint32_t SAC_TARGETS_STREAM = 0x5A7Au;  // ... of rr_sac_targets' draws: one (seed, call) never correlates acting and learning
 constexpr float SAC_SIGMA_MIN = 1e-6f, SAC_SIGMA_MAX = 1.0f;  // ActorNetwork.forward: clamp(sigma, reparam_noise, 1)
 constexpr float SAC_LOG_EPS = 1e-6f;                          // ... sample_normal: log(1 - a^2 + reparam_noise)
 constexpr float SAC_TWO_PI = 6.2831853071795865f, SAC_HALF_LOG_TWO_PI = 0.91893853320467274f;
@@ -24,9 +27,9 @@ RR_DQN_HD void sac_box_muller(float u1, float u2, float &z0, float &z1) {
     z0 = r * cosf(a);
     z1 = r * sinf(a);
 }
-// the four draws of row `row` in call `call`: Philox4x32-10, counter (row, call, SAC_STREAM, 0), key = seed (low word, high word)
-RR_DQN_HD void sac_draw(uint32_t row, uint32_t call, uint64_t seed, float z[4]) {
-    uint32_t w[4] = { row, call, SAC_STREAM, 0u };
+// the four draws of row `row` in call `call`: Philox4x32-10, counter (row, call, stream, 0), key = seed (low word, high word)
+RR_DQN_HD void sac_draw(uint32_t row, uint32_t call, uint64_t seed, float z[4], uint32_t stream = SAC_STREAM) {
+    uint32_t w[4] = { row, call, stream, 0u };
     philox4x32_10(w, (uint32_t)seed, (uint32_t)(seed >> 32));
     float u1, u2;
     sac_uniforms(w[0], w[1], u1, u2);
@@ -40,6 +43,17 @@ RR_DQN_HD float sac_action(float mu, float sigma, float z, float max_action) { r
 // Normal(mu, sigma).log_prob(mu + sigma z) - log(1 - a^2 + 1e-6) of one component (a: the SCALED action, as the reference has it)
 RR_DQN_HD float sac_log_prob_term(float sigma, float z, float a) {
     return -0.5f * z * z - logf(sigma) - SAC_HALF_LOG_TWO_PI - logf(1.0f - a * a + SAC_LOG_EPS);
+}
+
+// ---- rr_sac_targets
+// the gather's bounds rule: ring row i may be used as an address
+RR_DQN_HD bool sac_ring_row_ok(int64_t i, int64_t mem_rows) { return i >= 0 && i < mem_rows; }
+// value_target = min(Q1, Q2) - log pi: one subtraction of the fp32 numbers the windows report
+RR_DQN_HD float sac_value_target(float q1, float q2, float log_prob) { return fminf(q1, q2) - log_prob; }
+// q_hat = reward_scale r + gamma (done ? 0 : V_target(s')): two rounded products and their rounded sum (no contraction)
+RR_DQN_HD float sac_q_hat(float reward_scale, float r, float gamma, bool done, float v_next) {
+    const float a = reward_scale * r, b = gamma * (done ? 0.0f : v_next);
+    return a + b;
 }
 
 } // namespace rr

@@ -8,9 +8,11 @@ call handles all N arenas.
 
 Acting -- every row, every vector step -- is rr_sac_act where it applies (one HIP kernel: the hidden layers on the fp32 matrix cores, the
 draw, the squash; csrc/rr_sac.hip); anything else, and fused=False, goes through the torch modules.  Learning is PyTorch autograd on the
-same parameters (five small MLPs).  No convergence claim is made for this trainer.
+same parameters (five small MLPs); with fused_targets=True its no-grad half -- the replay gathers, the policy sample, both critics on it and
+the target value net: value_target and q_hat -- is rr_sac_targets, one HIP kernel, and autograd keeps the backward passes.  No convergence
+claim is made for this trainer.
 
-    python -m roborugby_amd.sac --num-envs 65536 --steps 300 --preset T --checkpoint runs/sac_T.pt
+    python -m roborugby_amd.sac --num-envs 65536 --steps 300 --preset T --checkpoint runs/sac_T.pt [--fused-targets]
 """
 import argparse
 import copy
@@ -97,16 +99,20 @@ class ActorNetwork(nn.Module):
 class BatchedSACAgent:
     """Agent (Training_SAC_pytorch.py:243-388) with [N]-batched choose_action / remember and a device replay.
     fused: None = rr_sac_act whenever it applies (a GPU, the 11-256-256 actor, n_actions 2 or 4); False = the torch path always.
+    fused_targets: True = learn() takes value_target and q_hat from rr_sac_targets (one launch on the rings; the value target's noise is
+    then the kernel's draw under (seed, learn call) instead of a torch.randn from the agent's generator); needs what fused=True needs and
+    batch_size % 64 == 0.  Default False.
     The replay is a ring on the device with float actions [M, A], written with torch indexing for the rows whose `valid` is set."""
 
     def __init__(self, alpha=1e-4, beta=1e-4, input_dims=11, n_actions=2, max_action=1.0, gamma=.99, max_mem_size=1 << 20, tau=.005,
-                 fc1_dims=256, fc2_dims=256, batch_size=4096, reward_scale=2.0, device="cpu", seed=0, fused=None):
+                 fc1_dims=256, fc2_dims=256, batch_size=4096, reward_scale=2.0, device="cpu", seed=0, fused=None, fused_targets=False):
         self.gamma, self.tau, self.scale = gamma, tau, reward_scale
         self.n_actions, self.input_dims, self.max_action = int(n_actions), int(input_dims), float(max_action)
         self.mem_size, self.batch_size = int(max_mem_size), int(batch_size)
         self.device = torch.device(device)
         self.mem_cntr, self.updates, self.last_losses = 0, 0, None
         self._act_calls = 0  # fused choose_action calls so far: keys the kernel's draws (checkpointed)
+        self._learn_calls = 0  # learn() calls through rr_sac_targets so far: keys that kernel's draws (checkpointed)
         self._seed = int(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
@@ -131,7 +137,11 @@ class BatchedSACAgent:
         self.fused = can_fuse if fused is None else bool(fused)
         if self.fused and not can_fuse:
             raise ValueError("fused=True needs a GPU, the reference's 11-256-256 actor and 2 or 4 actions")
-        self._dqn = _lib.DqnHandle(d) if self.fused else None
+        self.fused_targets = bool(fused_targets)
+        if self.fused_targets and not (can_fuse and self.batch_size > 0 and self.batch_size % 64 == 0):
+            raise ValueError("fused_targets=True needs a GPU, the reference's 11-256-256 networks, 2 or 4 actions and a batch_size that is a "
+                             "positive multiple of 64")
+        self._dqn = _lib.DqnHandle(d) if self.fused or self.fused_targets else None
 
     # what dqn._train_result reads of an agent: SAC has no epsilon schedule, and its target follows every learn() (soft update)
     epsilon, target_update_freq = 0.0, 0
@@ -197,19 +207,49 @@ class BatchedSACAgent:
     def losses(self, batch, noise_value, noise_actor):
         """(value_loss, actor_loss, critic_loss) of Agent.learn (:344-383) on batch = (state, action, reward, new_state, done), a function
         of the batch and the two standard normal tensors [B, A]: noise_value of the non-reparameterised sample behind the value target,
-        noise_actor of the reparameterised one behind the actor loss."""
-        state, action, reward, state_, done = batch
+        noise_actor of the reparameterised one behind the actor loss.  The composition of targets() and losses_given_targets()."""
+        value_target, q_hat = self.targets(batch, noise_value)
+        return self.losses_given_targets(batch[0], batch[1], value_target, q_hat, noise_actor)
+
+    @torch.no_grad()
+    def targets(self, batch, noise_value):
+        """The no-grad half of losses(), the torch path: (value_target, q_hat) [B] each.  value_target = min(Q1, Q2)(s, a~) - log pi(a~ | s)
+        with a~ the non-reparameterised sample under noise_value, q_hat = reward_scale r + gamma (done ? 0 : V_target(s'))."""
+        state, _, reward, state_, done = batch
+        value_ = self.target_value(state_).view(-1).masked_fill(done, 0.0)
+        # (the reference leaves this target attached and zeroes what it sends into the actor and the critics before they are used)
+        actions, log_probs = self.actor.sample_normal(state, noise_value, reparameterize=False)
+        value_target = torch.min(self.critic_1(state, actions), self.critic_2(state, actions)).view(-1) - log_probs
+        q_hat = self.scale * reward + self.gamma * value_
+        return value_target, q_hat
+
+    def targets_fused(self, batch_index, noise_value=None, mem_rows=None, **windows):
+        """targets() of the ring rows batch_index (int64 [B], B a multiple of 64) through rr_sac_targets: (value_target, q_hat, state,
+        action) with state / action the gathered rows.  noise_value None: the kernel draws under (seed, _learn_calls); windows: tensors
+        for the kernel's optional outputs (policy_action, log_prob, head, noise_out, q1, q2, v_next)."""
+        if self._dqn is None:
+            raise ValueError("targets_fused needs an agent built with fused or fused_targets on a GPU")
+        B, d = int(batch_index.shape[0]), self.device
+        assert batch_index.dtype == torch.int64 and batch_index.is_contiguous() and batch_index.device == self.state_memory.device
+        assert noise_value is None or (noise_value.dtype == torch.float32 and noise_value.is_contiguous() and tuple(noise_value.shape) == (B, self.n_actions))
+        nets = [list(n.parameters()) for n in (self.actor, self.critic_1, self.critic_2, self.target_value)]
+        assert all(p.is_contiguous() and p.dtype == torch.float32 for n in nets for p in n)
+        value_target, q_hat = torch.empty(B, device=d), torch.empty(B, device=d)
+        state, action = torch.empty(B, self.input_dims, device=d), torch.empty(B, self.n_actions, device=d)
+        rings = (self.state_memory, self.new_state_memory, self.action_memory, self.reward_memory, self.terminal_memory)
+        self._dqn.sac_targets(*nets, rings, min(self.mem_cntr, self.mem_size) if mem_rows is None else mem_rows, B, self.n_actions,
+                              self.max_action, self.gamma, self.scale, value_target, q_hat, batch_index=batch_index, noise=noise_value,
+                              seed=self._seed, calls=self._learn_calls, state=state, action=action, **windows)
+        return value_target, q_hat, state, action
+
+    def losses_given_targets(self, state, action, value_target, q_hat, noise_actor):
+        """The autograd half of losses(): (value_loss, actor_loss, critic_loss) from the batch's states and actions, the two target
+        vectors [B] (constants) and the standard normal tensor [B, A] of the reparameterised sample behind the actor loss."""
         value = self.value(state).view(-1)
-        with torch.no_grad():
-            value_ = self.target_value(state_).view(-1).masked_fill(done, 0.0)
-            # (the reference leaves this target attached and zeroes what it sends into the actor and the critics before they are used)
-            actions, log_probs = self.actor.sample_normal(state, noise_value, reparameterize=False)
-            value_target = torch.min(self.critic_1(state, actions), self.critic_2(state, actions)).view(-1) - log_probs
         value_loss = 0.5 * F.mse_loss(value, value_target)
         actions, log_probs = self.actor.sample_normal(state, noise_actor, reparameterize=True)
         critic_value = torch.min(self.critic_1(state, actions), self.critic_2(state, actions)).view(-1)
         actor_loss = torch.mean(log_probs - critic_value)
-        q_hat = self.scale * reward + self.gamma * value_
         critic_loss = 0.5 * F.mse_loss(self.critic_1(state, action).view(-1), q_hat) + 0.5 * F.mse_loss(self.critic_2(state, action).view(-1), q_hat)
         return value_loss, actor_loss, critic_loss
 
@@ -225,11 +265,19 @@ class BatchedSACAgent:
         Each loss only steps its own network(s), and none depends on what an earlier step of the same call changed (the actor loss not on
         the value net, the critic loss on neither), so the three are computed on one forward and stepped in the reference's order.
         Returns the three losses (device scalars), None until the replay holds a batch.
-        The draws are made here -- the batch rows, then the value target's noise, then the actor loss's -- and learn_on does the rest."""
+        The draws are made here -- the batch rows, then the value target's noise, then the actor loss's -- and learn_on does the rest.
+        With fused_targets: the batch rows as above, then ONE rr_sac_targets launch on the rings (gathers, the value target's noise drawn
+        in the kernel under (seed, _learn_calls), value_target, q_hat), then the actor loss's noise from the generator, the autograd
+        half on the kernel's gathered rows, the same three steps and soft update."""
         if self.mem_cntr < self.batch_size:
             return None
         max_mem = min(self.mem_cntr, self.mem_size)
         idx = torch.randint(0, max_mem, (self.batch_size,), generator=self.gen, device=self.device)
+        if self.fused_targets:
+            self._learn_calls += 1
+            value_target, q_hat, state, action = self.targets_fused(idx, mem_rows=max_mem)
+            noise_actor = torch.randn((self.batch_size, self.n_actions), generator=self.gen, device=self.device)
+            return self._step(self.losses_given_targets(state, action, value_target, q_hat, noise_actor))
         batch = (self.state_memory[idx], self.action_memory[idx], self.reward_memory[idx], self.new_state_memory[idx], self.terminal_memory[idx])
         shape = (self.batch_size, self.n_actions)
         noise_value = torch.randn(shape, generator=self.gen, device=self.device)
@@ -239,7 +287,11 @@ class BatchedSACAgent:
     def learn_on(self, batch, noise_value, noise_actor):
         """learn() after its draws, a function of the agent's state and its arguments alone: the losses of batch = (state, action, reward,
         new_state, done) under the two standard normal tensors [B, A], the value, actor and critic steps, the soft update, the counters."""
-        value_loss, actor_loss, critic_loss = self.losses(batch, noise_value, noise_actor)
+        return self._step(self.losses(batch, noise_value, noise_actor))
+
+    def _step(self, losses):
+        """the value, actor and critic steps on their losses, the soft update, the counters"""
+        value_loss, actor_loss, critic_loss = losses
         for loss, opt in ((value_loss, self.value_optimizer), (actor_loss, self.actor_optimizer), (critic_loss, self.critic_optimizer)):
             opt.zero_grad(set_to_none=True)
             loss.backward(inputs=[p for g in opt.param_groups for p in g["params"]])
@@ -256,7 +308,8 @@ class BatchedSACAgent:
 
     def state_dict(self):
         sd = {k: getattr(self, k).state_dict() for k in self._NETS + self._OPTS}
-        sd.update(kind="sac", n_actions=self.n_actions, mem_cntr=self.mem_cntr, updates=self.updates, act_calls=self._act_calls, fused=self.fused)
+        sd.update(kind="sac", n_actions=self.n_actions, mem_cntr=self.mem_cntr, updates=self.updates, act_calls=self._act_calls, fused=self.fused,
+                  learn_calls=self._learn_calls)
         return sd
 
     def load_state_dict(self, sd):
@@ -265,15 +318,18 @@ class BatchedSACAgent:
         for k in self._NETS + self._OPTS:
             getattr(self, k).load_state_dict(sd[k])
         self._act_calls = int(sd.get("act_calls", 0))
+        self._learn_calls = int(sd.get("learn_calls", 0))
         self.updates = int(sd.get("updates", 0))  # (the replay is not checkpointed: mem_cntr restarts at what this process has stored)
 
 
 def train_sac(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkpoint=None, resume=None, log_every=50, learn=True,
-              mem_size=1 << 20, dtype="f64", updates_per_step=1, batch_size=4096, out=None, step_budget_clocks=0, fused=None):
+              mem_size=1 << 20, dtype="f64", updates_per_step=1, batch_size=4096, out=None, step_budget_clocks=0, fused=None,
+              fused_targets=False):
     """The main loop of Training_SAC_pytorch.py over a batched env with action_mode="thrust": per vector step, serial on one stream,
     choose_action (rr_sac_act: one launch for every arena) -> env.step_thrust (the agent drives the happy team: A = 2 * nr_happy
     columns) -> remember the rows that were transitions (a row whose status has WAS_RESET was only re-placed and ends none) ->
-    updates_per_step x learn().  Returns dqn.train()'s result dict (+ n_actions, fused_act, mem_cntr, act_calls and the three losses).
+    updates_per_step x learn() (fused_targets: its no-grad half through rr_sac_targets).  Returns dqn.train()'s result dict (+ n_actions,
+    fused_act, fused_targets, mem_cntr, act_calls and the three losses).
     The budgeted step is not wired to this trainer: step_budget_clocks != 0 is refused."""
     import roborugby_amd as rr
     from .dqn import _save_checkpoint, _train_result, _write_result
@@ -282,7 +338,8 @@ def train_sac(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, ch
     env = rr.BatchedRoboRugbyEnv(num_envs, preset=preset, device=device, seed=seed, dtype=dtype, action_mode="thrust")
     A = env.action_space.shape[0]
     agent = BatchedSACAgent(input_dims=env.observation_space.shape[0], n_actions=A, max_action=float(env.action_space.high.max()),
-                            max_mem_size=mem_size, batch_size=batch_size, device=device, seed=seed, fused=fused)
+                            max_mem_size=mem_size, batch_size=batch_size, device=device, seed=seed, fused=fused,
+                            fused_targets=fused_targets)
     if resume:
         ck = torch.load(resume, map_location=device)
         agent.load_state_dict(ck["agent"])
@@ -317,7 +374,8 @@ def train_sac(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, ch
     res = _train_result(agent, env, num_envs * steps, dt, steps, int(real_rows.item()), 0, updates_per_step if learn else 0, num_envs, False,
                         0.0, 0.0, False, float(score_sum.mean() / max(steps, 1)), preset, dtype, [])
     ls = [float(x) for x in agent.last_losses] if agent.last_losses else [None] * 3
-    res.update(mode="train_sac", n_actions=A, fused_act=bool(agent.fused), mem_cntr=agent.mem_cntr, act_calls=agent._act_calls,
+    res.update(mode="train_sac", n_actions=A, fused_act=bool(agent.fused), fused_targets=bool(agent.fused_targets), mem_cntr=agent.mem_cntr,
+               act_calls=agent._act_calls,
                tau=agent.tau, reward_scale=agent.scale, value_loss=ls[0], actor_loss=ls[1], critic_loss=ls[2], resumed_from=resume)
     agent.close()
     env.close()
@@ -341,9 +399,12 @@ def main():
     ap.add_argument("--log-every", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-fused", action="store_true", help="choose_action through the torch modules instead of rr_sac_act")
+    ap.add_argument("--fused-targets", action="store_true",
+                    help="learn()'s no-grad half (replay gathers, policy sample, critics, target value net) through rr_sac_targets")
     a = ap.parse_args()
     res = train_sac(a.num_envs, a.steps, a.preset, a.device, a.seed, a.checkpoint, a.resume, a.log_every, not a.no_learn,
-                    updates_per_step=a.updates_per_step, batch_size=a.batch_size, out=a.out, fused=False if a.no_fused else None)
+                    updates_per_step=a.updates_per_step, batch_size=a.batch_size, out=a.out, fused=False if a.no_fused else None,
+                    fused_targets=a.fused_targets)
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
 
 

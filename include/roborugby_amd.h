@@ -540,6 +540,50 @@ typedef struct rr_sac_targets_args {
 } rr_sac_targets_args;
 int rr_sac_targets(rr_dqn *dqn, const rr_sac_targets_args *args, void *stream);
 
+/* ---- three of the four backward passes of the SAC agent's learn (roborugby_amd/csrc/rr_sac.hip k_sac_grads, k_sac_grads_reduce;
+ * roborugby_amd/sac.py BatchedSACAgent.grads_fused): the gradients of the value loss and of the critic loss of Agent.learn
+ * (Training_SAC_pytorch.py:344-383) with respect to the parameters of `value`, `critic_1` and `critic_2`, given the two target vectors
+ * rr_sac_targets hands out, in one fused launch on the fp32 matrix cores plus one reduce launch -- no autograd:
+ *   value_loss  = 0.5 * mse_loss(ValueNetwork(s), value_target)                                                     = loss[0]
+ *   critic_loss = 0.5 * mse_loss(CriticNetwork_1([s, a]), q_hat) + 0.5 * mse_loss(CriticNetwork_2([s, a]), q_hat)   = loss[1] + loss[2]
+ * The actor loss and its backward stay with the caller (autograd): it goes through both critics to the action and back through the
+ * squashed policy.  No optimizer step is made here; the parameters are only read.
+ * Inputs, all dense fp32: state [B,11], action [B,A], value_target [B], q_hat [B] (rr_sac_targets' outputs of those names, or any other
+ * rows), and the six tensors of each net in rr_sac_targets_args' order and torch.nn.Linear layouts, read as they stand at call time.
+ * Outputs: per net six gradient tensors in the same order and layouts, caller-owned, and loss [3].
+ * THE ARITHMETIC (this is the specification; tests/sac_grads_ref.py is it in numpy float64):
+ *   For net j with input x (value: s; critics: [s, a]) and target y (value: value_target; critics: q_hat), f = the fp32 forward:
+ *     rr_sac_targets' hidden layers (fp32 products summed in fp32, in no particular order), then an fp32 dot plus the fp32 bias for the
+ *     single output.  The output gradient of row b is d_b = (f_b - y_b) / B: one subtraction, one multiplication by fl(1 / B).
+ *   loss[j] = 0.5 * mean_b (f_b - y_b)^2.
+ *   The gradients are those of loss[j] by the chain rule through Linear -> ReLU -> Linear -> ReLU -> Linear; the ReLU derivative is
+ *     h > 0 (0 at h == 0, as torch has it).  Every sum is fp32, in no particular order inside a 64-row tile; the tiles of a chunk are
+ *     accumulated in order, the chunks summed in order.
+ * Work split: with G workgroups (one per CU; RR_DQN_WGS bounds G) each net has C = max(1, G / 3) chunks, chunk c takes the 64-row tiles
+ * c, c + C, ...; only the min(C, B / 64) chunks that have a tile enter the sum.
+ * Every element of every output is written by every call; nothing at or beyond row B is read; no atomics; the handle keeps nothing but a
+ * scratch for the per-chunk partial sums (allocated by the first call, grown by a call that needs more).  The results are bit-identical
+ * from call to call for a given (B, G).  They are NOT promised identical across grid sizes (RR_DQN_WGS): the partial sums regroup.
+ * One stream per handle at a time: the scratch is the handle's, so calls on two streams would share it; and the first call, or one that
+ * needs more slots than any before, calls hipFree / hipMalloc -- make it outside a stream capture.
+ * Inputs and parameters must be finite: a NaN row -- rr_sac_targets writes one for a ring row outside the rings -- makes the gradients
+ * NaN; nothing here looks for it.
+ * Returns -1 (message "rr_sac_grads: ...": rr_dqn_last_error) and launches nothing for: a null handle, args or required pointer (every
+ * params and grads entry, state, action, value_target, q_hat, loss), a wrong struct_size, a batch that is not a positive
+ * multiple of 64, n_actions outside {2, 4}, non-zero flags. */
+typedef struct rr_sac_grads_args {
+    int32_t struct_size;               /* = sizeof(rr_sac_grads_args) */
+    int32_t batch;                     /* B: a positive multiple of 64 */
+    int32_t n_actions;                 /* A: 2 or 4 */
+    int32_t flags;                     /* 0 */
+    const float *value[6];             /* fc1.weight [256,11], fc1.bias, fc2.weight [256,256], fc2.bias, v.weight [1,256], v.bias [1] */
+    const float *critic_1[6], *critic_2[6];   /* fc1.weight [256, 11+A], fc1.bias, fc2.weight, fc2.bias, q.weight [1,256], q.bias [1] */
+    const float *state, *action, *value_target, *q_hat;  /* [B,11], [B,A], [B], [B] */
+    float *grad_value[6], *grad_critic_1[6], *grad_critic_2[6];  /* the gradients, in the parameters' order and layouts */
+    float *loss;                       /* [3]: 0.5 * mse of value, critic_1, critic_2 */
+} rr_sac_grads_args;
+int rr_sac_grads(rr_dqn *dqn, const rr_sac_grads_args *args, void *stream);
+
 /* ---- the frame-sharing pixel replay (roborugby_amd/csrc/rr_frames.hpp, rr_frames.hip; roborugby_amd/frame_replay.py FrameReplay): a ring
  * that stores every frame ONCE instead of two whole stacked observations per transition.  The caller owns the ring (device memory):
  *   frames  u8  [slots, rows, frame_bytes]   the newest frame of every row after push k, in slot k % slots

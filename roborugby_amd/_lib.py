@@ -54,6 +54,17 @@ class RRSacTargetsArgs(C.Structure):
     ]
 
 
+class RRSacGradsArgs(C.Structure):
+    """rr_sac_grads_args (include/roborugby_amd.h)"""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("batch", C.c_int32), ("n_actions", C.c_int32), ("flags", C.c_int32),
+        ("value", C.c_void_p * 6), ("critic_1", C.c_void_p * 6), ("critic_2", C.c_void_p * 6),
+        ("state", C.c_void_p), ("action", C.c_void_p), ("value_target", C.c_void_p), ("q_hat", C.c_void_p),
+        ("grad_value", C.c_void_p * 6), ("grad_critic_1", C.c_void_p * 6), ("grad_critic_2", C.c_void_p * 6),
+        ("loss", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/roborugby_amd.h declares
 _vp = C.c_void_p
 SYMBOLS = {
@@ -109,6 +120,7 @@ SYMBOLS = {
     "rr_cnn_act": (C.c_int, [_vp, C.POINTER(_vp * 8), _vp, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
     "rr_sac_act": (C.c_int, [_vp, C.POINTER(_vp * 8), _vp, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "rr_sac_targets": (C.c_int, [_vp, C.POINTER(RRSacTargetsArgs), _vp]),
+    "rr_sac_grads": (C.c_int, [_vp, C.POINTER(RRSacGradsArgs), _vp]),
     "rr_frames_push": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rr_frames_sample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_uint64,
                                    C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -308,3 +320,21 @@ class DqnHandle(_Handle):
         if windows:
             raise TypeError(f"sac_targets: unknown windows {sorted(windows)}")
         self.launch("rr_sac_targets", C.byref(a))
+
+    def sac_grads(self, value, critic_1, critic_2, state, action, value_target, q_hat, batch, n_actions, grad_value, grad_critic_1,
+                  grad_critic_2, loss):
+        """rr_sac_grads: the gradients of the SAC value loss and critic loss in one fused launch (plus its reduce).  value, critic_1,
+        critic_2: six tensors each (rr_sac_targets' order); state [batch, 11], action [batch, n_actions], value_target, q_hat [batch]:
+        dense float32.  Written: grad_value, grad_critic_1, grad_critic_2 (six tensors each, the parameters' shapes) and loss [3] =
+        0.5 * mse of the value net, critic_1 and critic_2."""
+        a = RRSacGradsArgs()
+        a.struct_size, a.batch, a.n_actions, a.flags = C.sizeof(RRSacGradsArgs), int(batch), int(n_actions), 0
+        for field, tensors in (("value", value), ("critic_1", critic_1), ("critic_2", critic_2), ("grad_value", grad_value),
+                               ("grad_critic_1", grad_critic_1), ("grad_critic_2", grad_critic_2)):
+            arr = getattr(a, field)
+            if len(tensors) != len(arr):
+                raise ValueError(f"sac_grads: {field} takes {len(arr)} tensors, got {len(tensors)}")
+            for k, p in enumerate(tensors):
+                arr[k] = p.data_ptr()
+        a.state, a.action, a.value_target, a.q_hat, a.loss = ptr(state), ptr(action), ptr(value_target), ptr(q_hat), ptr(loss)
+        self.launch("rr_sac_grads", C.byref(a))

@@ -357,7 +357,7 @@ int rr_dqn_create(int32_t device, rr_dqn **out) {
     { const char *w = getenv("RR_DQN_WGS"); const int k = w ? atoi(w) : 0; if (k > 0 && k < cus) cus = k; }
     rr_dqn *d = new rr_dqn();
     d->device = device; d->nwg = cus; d->step = 0; d->partials = nullptr; d->m1 = nullptr; d->m2 = nullptr;
-    d->chunk_off = nullptr; d->chunk_cap = 0; d->cnn_weights = nullptr;
+    d->chunk_off = nullptr; d->chunk_cap = 0; d->cnn_weights = nullptr; d->sac_partials = nullptr; d->sac_cap = 0;
     hipError_t e = hipMalloc((void **)&d->partials, sizeof(float) * (size_t)P_STRIDE * (size_t)d->nwg);
     if (e == hipSuccess) e = hipMalloc((void **)&d->m1, sizeof(float) * P_STRIDE);
     if (e == hipSuccess) e = hipMalloc((void **)&d->m2, sizeof(float) * P_STRIDE);
@@ -380,6 +380,7 @@ int rr_dqn_destroy(rr_dqn *d) {
     (void)hipFree(d->partials); (void)hipFree(d->m1); (void)hipFree(d->m2);
     if (d->chunk_off) (void)hipFree(d->chunk_off);
     if (d->cnn_weights) (void)hipFree(d->cnn_weights);
+    if (d->sac_partials) (void)hipFree(d->sac_partials);
     delete d;
     return 0;
 }

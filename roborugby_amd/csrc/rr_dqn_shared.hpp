@@ -19,6 +19,8 @@ struct rr_dqn {
     uint32_t *chunk_off; // rr_dqn_store's per-chunk offsets (grown on demand; a call with a larger batch than any before allocates)
     size_t chunk_cap;
     uint16_t *cnn_weights; // rr_cnn_act's bf16 copy of the weights, rewritten by every call (allocated by the first)
+    float *sac_partials;   // rr_sac_grads' per-(net, chunk) partial gradients (allocated by the first call, grown by a call that needs more slots)
+    size_t sac_cap;        // ... its size in slots
 };
 
 // sets the string rr_dqn_last_error returns (thread-local, rr_dqn.hip) and hands `code` back

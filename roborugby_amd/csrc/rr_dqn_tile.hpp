@@ -1,7 +1,8 @@
 // rr_dqn_tile.hpp -- the two 256-wide hidden layers of the reference's MLPs (Linear K -> 256 -> 256, ReLU; K = 11, or 11 + A for the SAC
 // critics) for one 64-row tile on the fp32 matrix cores, as the kernels behind the rr_dqn handle share them: rr_dqn.hip (k_dqn_fwd_bwd,
-// k_dqn_act: the Q network) and rr_sac.hip (k_sac_act: the SAC actor; k_sac_targets: actor, critics and target value net).  Device code
-// only; what a tile's head does with X1 is the including kernel's business.
+// k_dqn_act: the Q network) and rr_sac.hip (k_sac_act: the SAC actor; k_sac_targets: actor, critics and target value net; k_sac_grads:
+// the value net and the critics, forward and backward).  Device code only; what a tile's head does with X1 is the including kernel's
+// business.
 #pragma once
 #include <hip/hip_runtime.h>
 

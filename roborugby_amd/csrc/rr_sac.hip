@@ -21,6 +21,29 @@
 //               zeros and written as NaN.
 // No atomics, nothing kept in the handle.  C-ABI and the arithmetic's specification: rr_sac_act / rr_sac_targets in
 // include/roborugby_amd.h.
+//
+// ... and three of the four backward passes of Agent.learn (:344-383): the value net and the two critics are each a Linear K -> 256 ->
+// 256 -> 1 MLP regressed onto a constant target vector with 0.5 * mse_loss (K = 11, 11 + A), which needs no autograd:
+//
+//   k_sac_grads   rr_dqn.hip's k_dqn_fwd_bwd with a scalar head and no target net: 256 threads, one workgroup per CU, 64-row tiles, the
+//               activations transposed in LDS at row stride 65, the dW2 accumulators resident in registers over a work item's tiles
+//               (256 per lane), dW1 / dWo / db* per-thread VALU accumulators.  A workgroup's accumulators belong to one net at a time,
+//               so the work item is (net, chunk): with G workgroups a net has C = max(1, G / 3) chunks, the items are numbered net-major
+//               and dealt round-robin (G < 3: a workgroup takes several, one after the other, and zeroes its accumulators in between);
+//               item (net, c) takes the tiles c, c + C, ... and writes ONE partial into slot (net, c); a chunk without a tile writes
+//               nothing.  min(G, 3 C) workgroups are launched: one that would have no item (G = 7: six items) is not, one whose chunk has
+//               no tile (B = 4,096 on 256 CUs: 63 of 255) exits at once.  Per tile: inputs [s] or [s, a] -> hidden_tile<K> -> the single output f (single_head) -> d = (f - y) / B,
+//               loss += (f - y)^2 -> fc3 backward (VALU; relu' = h > 0 as torch has it) -> dW2 += dh2^T h1 (MFMA) -> dh1 = (dh2 W2) *
+//               relu' (MFMA) -> dW1, db1 (VALU).
+//   k_sac_grads_reduce   sums a net's min(C, B / 64) slots in chunk order (fp32), scatters the sums into the caller's six tensors per net
+//               and writes loss_j = 0.5 * sum (f - y)^2 / B.
+// THE CONTRACT: for net j with input x and target y, f = the fp32 forward (hidden_tile's layers, then an fp32 dot plus the bias); the
+// output gradient of a row is d = (f - y) / B (one subtraction, one multiplication by fl(1 / B)); loss_j = 0.5 * mean (f - y)^2, so
+// value_loss = loss[0] and critic_loss = loss[1] + loss[2]; every sum is fp32, in no particular order inside a tile.  No atomics; every
+// element of every output is written by every call; the handle keeps nothing but the partials scratch (allocated by the first call,
+// grown by a call that needs more slots).  Bit-identical from call to call for a given (B, G); NOT across grid sizes (RR_DQN_WGS): the
+// partial sums regroup.  Inputs must be finite: a NaN row (rr_sac_targets writes one for a ring row outside the rings) makes the
+// gradients NaN, and nothing here handles it.  C-ABI: rr_sac_grads in include/roborugby_amd.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
@@ -134,7 +157,8 @@ __device__ __forceinline__ void gather_tile(const TargetsArgs &g, const float *r
 
 // the single output of a net whose second hidden layer is in X1: wavefront w sums the products k = 64 w .. 64 w + 63 of row = lane in
 // order, lane `row` of wavefront 0 adds the four partial sums in order and the bias -> out[row] (LDS).  Ends behind a barrier.
-__device__ __forceinline__ void single_head(const Mlp1 &net, const float *X1, float *part, float *out, int t, int w, int l) {
+template <class NetT>
+__device__ __forceinline__ void single_head(const NetT &net, const float *X1, float *part, float *out, int t, int w, int l) {
     const float *wo = net.wo + w * (H / 4);
     float q = 0.0f;
 #pragma unroll 8
@@ -241,7 +265,258 @@ __global__ __launch_bounds__(NT, 1) void k_sac_targets(TargetsArgs g) {
     }
 }
 
+// ---- rr_sac_grads
+// (a type of its own: hidden_tile and single_head are instantiated apart from k_sac_targets' -- the optimiser specialises a shared
+// instantiation for all of its callers together, and k_sac_targets keeps the code it had)
+struct GradNet : Mlp1 {};
+struct GradsArgs {
+    GradNet value, critic_1, critic_2;
+    const float *state, *action, *value_target, *q_hat;
+    int batch, chunks, slots;  // chunks per net (C); slots per net in `partials` = min(C, tiles)
+    float *partials;
+};
+struct GradsOut { float *grad[rr::SAC_GRADS_NETS][6]; float *loss; };
+
+// one work item: the tiles chunk, chunk + chunks, ... of one net with K inputs (K odd: the pad row of S is row K), regressed onto
+// `target`; the partial gradient goes to `out` (a slot: rr::sac_grads_layout(K, H)).  Ends behind a barrier: the next item may reuse LDS.
+template <int K>
+__device__ __forceinline__ void grads_item(const GradNet &net, const float *state, const float *action, const float *target, int batch, int chunk,
+                                           int chunks, float *out, float *X0, float *X1, float *S, float *P, float *QV, float *DQ, float *RED) {
+    static_assert(K % 2 == 1 && K >= IN && K <= 15, "S holds K + 1 <= 16 rows");
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // gradient accumulators that stay in registers over all of this item's tiles
+    f16v dw2[16]; // [it (i-tile 2w+it)][jt]: dW2[i][j], i = out feature of fc2, j = in feature
+#pragma unroll
+    for (int q = 0; q < 16; q++) dw2[q] = (f16v)0.0f;
+    float dw1[K];
+#pragma unroll
+    for (int q = 0; q < K; q++) dw1[q] = 0.0f;
+    float dwo = 0.0f, db1 = 0.0f, db2 = 0.0f, dbo = 0.0f, loss = 0.0f;
+    const float wo_t = net.wo[threadIdx.x];
+    const float inv_b = 1.0f / (float)batch;
+    const int ntiles = batch / TM;
+    for (int tile = chunk; tile < ntiles; tile += chunks) {
+        // (the lane index is opaque per tile: hoisted out of this loop, a tile's address arithmetic does not fit next to the 256
+        // accumulators -- it is cheap to redo and costly to spill)
+        int l = lane;
+        asm volatile("" : "+v"(l));
+        const int t = w * 64 + l, half = l >> 5, c = l & 31;
+        // ---- the tile's inputs transposed into LDS: the state, for a critic the action behind it, the pad row
+        for (int e = t; e < TM * IN; e += NT) {
+            const int m = e / IN, ci = e - m * IN;
+            S[ci * LDX + m] = state[(size_t)(tile * TM + m) * IN + ci];
+        }
+        if (K > IN) {
+            constexpr int A = K > IN ? K - IN : 1;
+            for (int e = t; e < TM * A; e += NT) {
+                const int m = e / A, ci = e - m * A;
+                S[(IN + ci) * LDX + m] = action[(size_t)tile * TM * A + e];
+            }
+        }
+        if (t < TM) S[K * LDX + t] = 0.0f;
+        __syncthreads();
+        // ---- forward: h1 -> X0, h2 -> X1, f -> QV; the output gradient d = (f - y) / B
+        hidden_tile<K>(net, S, X0, X1, w, half, c);
+        single_head(net, X1, P, QV, t, w, l);
+        if (t < TM) {
+            const float diff = QV[t] - target[tile * TM + t];
+            DQ[t] = diff * inv_b;
+            loss += diff * diff;
+        }
+        __syncthreads();
+        // ---- fc3 backward (one output): thread t owns hidden unit n = t.  dWo[n] += d h2, then X1 <- dh2 = d Wo[n] relu'(h2)
+        {
+            float *row = &X1[t * LDX];
+#pragma unroll 4
+            for (int m = 0; m < TM; m++) {
+                const float d = DQ[m];   // wave-uniform: LDS broadcast
+                const float h = row[m];
+                dwo += d * h;
+                const float gr = h > 0.0f ? d * wo_t : 0.0f;
+                row[m] = gr;
+                db2 += gr;
+            }
+            if (t == 0) {
+#pragma unroll 4
+                for (int m = 0; m < TM; m++) dbo += DQ[m];
+            }
+        }
+        __syncthreads();
+        // ---- dW2[i][j] += sum_m dh2[m][i] h1[m][j]: reduction over the tile's 64 samples, two per MFMA
+#pragma unroll 2
+        for (int p = 0; p < TM / 2; p++) {
+            const int mm = 2 * p + half;
+            const float a0 = X1[((2 * w) * 32 + c) * LDX + mm], a1 = X1[((2 * w + 1) * 32 + c) * LDX + mm];
+#pragma unroll
+            for (int jt = 0; jt < 8; jt++) {
+                const float b = X0[(jt * 32 + c) * LDX + mm];
+                dw2[jt] = mfma(a0, b, dw2[jt]);
+                dw2[8 + jt] = mfma(a1, b, dw2[8 + jt]);
+            }
+        }
+        // ---- dh1[m][k] = sum_n dh2[m][n] W2[n][k] (then * relu'(h1)): output k-tiles {2w, 2w+1} x m-tiles {0, 1}
+        {
+            f16v acc[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) acc[q] = (f16v)0.0f;
+            const float *w2c0 = net.w2 + (2 * w) * 32 + c, *w2c1 = net.w2 + (2 * w + 1) * 32 + c;
+#pragma unroll 4
+            for (int np = 0; np < H / 2; np++) {
+                const int n = 2 * np + half;
+                const float a0 = X1[n * LDX + c], a1 = X1[n * LDX + 32 + c];
+                const float b0 = w2c0[n * H], b1 = w2c1[n * H];
+                acc[0] = mfma(a0, b0, acc[0]);
+                acc[1] = mfma(a1, b0, acc[1]);
+                acc[2] = mfma(a0, b1, acc[2]);
+                acc[3] = mfma(a1, b1, acc[3]);
+            }
+            __syncthreads(); // every wavefront has read h1 (X0) for dW2: it can be overwritten with dh1 now
+#pragma unroll
+            for (int kt = 0; kt < 2; kt++) {
+                const int k = (2 * w + kt) * 32 + c;
+#pragma unroll
+                for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        float *px = &X0[k * LDX + mt * 32 + acc_row(r, half)];
+                        *px = *px > 0.0f ? acc[kt * 2 + mt][r] : 0.0f;
+                    }
+            }
+        }
+        __syncthreads();
+        // ---- fc1 backward: thread t owns hidden unit k = t: db1, dW1[k][:] += dh1[m][k] x[m][:]
+        {
+            const float *row = &X0[t * LDX];
+#pragma unroll 4
+            for (int m = 0; m < TM; m++) {
+                const float gr = row[m];
+                db1 += gr;
+#pragma unroll
+                for (int ci = 0; ci < K; ci++) dw1[ci] = fmaf(gr, S[ci * LDX + m], dw1[ci]);
+            }
+        }
+        __syncthreads();
+    }
+    // ---- this item's partial gradient
+    int l = lane;
+    asm volatile("" : "+v"(l));  // (... nor do the 256 store addresses, computed ahead of the tile loop)
+    const int t = w * 64 + l, half = l >> 5, c = l & 31;
+    const rr::SacGradsLayout L = rr::sac_grads_layout(K, H);
+#pragma unroll
+    for (int it = 0; it < 2; it++)
+#pragma unroll
+        for (int jt = 0; jt < 8; jt++)
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                out[L.w2 + ((2 * w + it) * 32 + acc_row(r, half)) * H + jt * 32 + c] = dw2[it * 8 + jt][r];
+#pragma unroll
+    for (int ci = 0; ci < K; ci++) out[L.w1 + t * K + ci] = dw1[ci];
+    out[L.wo + t] = dwo;
+    out[L.b1 + t] = db1;
+    out[L.b2 + t] = db2;
+    if (t < TM) RED[t] = loss;
+    __syncthreads();
+    if (t == 0) {
+        out[L.bo] = dbo;
+        float s = 0.0f;
+        for (int q = 0; q < TM; q++) s += RED[q];
+        out[L.loss] = s;
+    }
+    __syncthreads();
+}
+
+template <int A>
+__global__ __launch_bounds__(NT, 1) void k_sac_grads(GradsArgs g) {
+    __shared__ float X0[H * LDX], X1[H * LDX], S[16 * LDX], P[4 * TM], QV[TM], DQ[TM], RED[TM];
+    const int C = g.chunks, G = (int)gridDim.x, items = rr::SAC_GRADS_NETS * C;
+    const int live = g.slots;  // chunks of a net that have a tile; the others have no slot and write nothing
+    // items 0 .. C-1 are the value net's, C .. 3C-1 the critics', dealt round-robin: a workgroup's value items first (one loop per
+    // input width: each keeps one set of accumulators)
+    for (int item = (int)blockIdx.x; item < C; item += G) {
+        if (item >= live) break;
+        grads_item<IN>(g.value, g.state, nullptr, g.value_target, g.batch, item, C, g.partials + (size_t)item * rr::SAC_GRADS_STRIDE, X0, X1, S, P,
+                       QV, DQ, RED);
+    }
+    const int first = C + (((int)blockIdx.x - C) % G + G) % G;  // this workgroup's first item >= C
+    for (int item = first; item < items; item += G) {
+        const int net = item / C, chunk = item - net * C;
+        if (chunk >= live) continue;
+        grads_item<IN + A>(net == 1 ? g.critic_1 : g.critic_2, g.state, g.action, g.q_hat, g.batch, chunk, C, g.partials +
+                           (size_t)(net * live + chunk) * rr::SAC_GRADS_STRIDE, X0, X1, S, P, QV, DQ, RED);
+    }
+}
+
+// element i of net blockIdx.y's slot layout: the sum of its `slots` partials in chunk order -> the caller's tensor (torch.nn.Linear
+// layouts), or the loss
+__global__ __launch_bounds__(256) void k_sac_grads_reduce(const float *partials, int slots, int n_actions, int batch, GradsOut o) {
+    const int net = (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const rr::SacGradsLayout L = rr::sac_grads_layout(net == 0 ? IN : IN + n_actions, H);
+    if (i >= L.count) return;
+    const float *p = partials + (size_t)net * slots * rr::SAC_GRADS_STRIDE + i;
+    float s = 0.0f;
+#pragma unroll 8
+    for (int ch = 0; ch < slots; ch++) s += p[(size_t)ch * rr::SAC_GRADS_STRIDE];  // (the loads do not wait for the sum: only the adds are a chain)
+    float *const *gr = o.grad[net];
+    if (i < L.w1) gr[2][i - L.w2] = s;
+    else if (i < L.wo) gr[0][i - L.w1] = s;
+    else if (i < L.b1) gr[4][i - L.wo] = s;
+    else if (i < L.b2) gr[1][i - L.b1] = s;
+    else if (i < L.bo) gr[3][i - L.b2] = s;
+    else if (i < L.loss) gr[5][0] = s;
+    else o.loss[net] = 0.5f * s / (float)batch;
+}
+
 } // namespace
+
+extern "C" int rr_sac_grads(rr_dqn *d, const rr_sac_grads_args *a, void *stream) {
+    if (!d || !a) return rr_dqn_fail(-1, "rr_sac_grads: null argument");
+    if (a->struct_size != (int32_t)sizeof(rr_sac_grads_args)) return rr_dqn_fail(-1, "rr_sac_grads: struct_size does not match this library");
+    for (int k = 0; k < 6; k++) {
+        if (!a->value[k] || !a->critic_1[k] || !a->critic_2[k]) return rr_dqn_fail(-1, "rr_sac_grads: null parameter pointer");
+        if (!a->grad_value[k] || !a->grad_critic_1[k] || !a->grad_critic_2[k]) return rr_dqn_fail(-1, "rr_sac_grads: null gradient pointer");
+    }
+    if (!a->state || !a->action || !a->value_target || !a->q_hat) return rr_dqn_fail(-1, "rr_sac_grads: state, action, value_target and q_hat are required");
+    if (!a->loss) return rr_dqn_fail(-1, "rr_sac_grads: loss is required");
+    if (a->batch <= 0 || a->batch % TM) return rr_dqn_fail(-1, "rr_sac_grads: batch must be a positive multiple of 64");
+    if (a->n_actions != 2 && a->n_actions != 4) return rr_dqn_fail(-1, "rr_sac_grads: n_actions must be 2 or 4");
+    if (a->flags) return rr_dqn_fail(-1, "rr_sac_grads: flags must be 0");
+    const auto mlp = [](const float *const p[6]) { return GradNet{ { p[0], p[1], p[2], p[3], p[4], p[5] } }; };
+    GradsArgs g;
+    g.value = mlp(a->value); g.critic_1 = mlp(a->critic_1); g.critic_2 = mlp(a->critic_2);
+    g.state = a->state; g.action = a->action; g.value_target = a->value_target; g.q_hat = a->q_hat;
+    g.batch = a->batch;
+    g.chunks = rr::sac_grads_chunks(d->nwg);
+    g.slots = rr::sac_grads_slots(g.chunks, a->batch / TM);
+    GradsOut o;
+    for (int k = 0; k < 6; k++) { o.grad[0][k] = a->grad_value[k]; o.grad[1][k] = a->grad_critic_1[k]; o.grad[2][k] = a->grad_critic_2[k]; }
+    o.loss = a->loss;
+    int prev = -1;
+    const bool sw = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
+    const size_t need = (size_t)rr::SAC_GRADS_NETS * (size_t)g.slots;
+    if (need > d->sac_cap) {  // (hipFree waits for the launches that still read the old scratch)
+        if (d->sac_partials) (void)hipFree(d->sac_partials);
+        d->sac_partials = nullptr; d->sac_cap = 0;
+        if (hipMalloc((void **)&d->sac_partials, sizeof(float) * rr::SAC_GRADS_STRIDE * need) != hipSuccess) {
+            d->sac_partials = nullptr;
+            if (sw) (void)hipSetDevice(prev);
+            return rr_dqn_fail(-3, "rr_sac_grads: out of device memory");
+        }
+        d->sac_cap = need;
+    }
+    g.partials = d->sac_partials;
+    const int items = rr::SAC_GRADS_NETS * g.chunks, nwg = items < d->nwg ? items : d->nwg;
+    if (a->n_actions == 2)
+        hipLaunchKernelGGL(k_sac_grads<2>, dim3(nwg), dim3(NT), 0, (hipStream_t)stream, g);
+    else
+        hipLaunchKernelGGL(k_sac_grads<4>, dim3(nwg), dim3(NT), 0, (hipStream_t)stream, g);
+    const int count = rr::sac_grads_layout(IN + 4, H).count;
+    hipLaunchKernelGGL(k_sac_grads_reduce, dim3((count + 255) / 256, rr::SAC_GRADS_NETS), dim3(256), 0, (hipStream_t)stream,
+                       (const float *)d->sac_partials, g.slots, (int)a->n_actions, (int)a->batch, o);
+    const hipError_t e = hipGetLastError();
+    if (sw) (void)hipSetDevice(prev);
+    if (e != hipSuccess) return rr_dqn_fail(-2, hipGetErrorString(e));
+    return 0;
+}
 
 extern "C" int rr_sac_act(rr_dqn *d, const float *const params[8], const float *obs, int32_t n, int32_t n_actions, float max_action,
                           int32_t flags, uint64_t seed, uint32_t call, float *actions, float *log_prob, float *head, float *noise,

@@ -1,8 +1,8 @@
 // rr_sac.hpp -- the per-row arithmetic of rr_sac_act's and rr_sac_targets' epilogues (include/roborugby_amd.h is the specification): the
 // standard normal draws of a row, the clamp of sigma, the squashed action and a component's share of the log-probability; the gather's
-// bounds rule and the two closing formulas of the learn targets.  Plain C++ as well as HIP: tests/emu/rr_sac_emu.cpp and
-// tests/emu/rr_sac_targets_emu.cpp compile these very functions with g++ and hold them to tests/sac_ref.py / tests/sac_targets_ref.py
-// without a GPU.
+// bounds rule and the two closing formulas of the learn targets; rr_sac_grads' work items and the layout of its partial slots.  Plain
+// C++ as well as HIP: tests/emu/rr_sac_emu.cpp and tests/emu/rr_sac_targets_emu.cpp compile the per-row functions with g++ and hold them
+// to tests/sac_ref.py / tests/sac_targets_ref.py without a GPU.
 #pragma once
 #include <math.h>
 #include "rr_dqn_shared.hpp"
@@ -55,5 +55,21 @@ RR_DQN_HD float sac_q_hat(float reward_scale, float r, float gamma, bool done, f
     const float a = reward_scale * r, b = gamma * (done ? 0.0f : v_next);
     return a + b;
 }
+
+// ---- rr_sac_grads
+// work items and partial slots: G workgroups give every net C = max(1, G / 3) chunks; chunk c of a net takes the 64-row tiles c, c + C,
+// ...; of a net's chunks only the first min(C, tiles) have a tile, and only those have a slot in the scratch (slot = net * slots + c)
+constexpr int SAC_GRADS_NETS = 3;  // value, critic_1, critic_2
+RR_DQN_HD int sac_grads_chunks(int nwg) { return nwg / SAC_GRADS_NETS > 1 ? nwg / SAC_GRADS_NETS : 1; }
+RR_DQN_HD int sac_grads_slots(int chunks, int tiles) { return chunks < tiles ? chunks : tiles; }
+// a slot (floats) of a net with K inputs and hidden width W: dW2 [W, W], dW1 [W, K], dWo [W], db1 [W], db2 [W], dbo, sum (f - y)^2
+struct SacGradsLayout { int w2, w1, wo, b1, b2, bo, loss, count; };
+RR_DQN_HD SacGradsLayout sac_grads_layout(int K, int W) {
+    SacGradsLayout s;
+    s.w2 = 0; s.w1 = s.w2 + W * W; s.wo = s.w1 + W * K; s.b1 = s.wo + W; s.b2 = s.b1 + W; s.bo = s.b2 + W; s.loss = s.bo + 1; s.count = s.loss + 1;
+    return s;
+}
+// the stride of a slot: the widest net's (K = 11 + 4) count, rounded up to 64 floats
+constexpr int SAC_GRADS_STRIDE = ((256 * 256 + 256 * 15 + 3 * 256 + 2 + 63) / 64) * 64;
 
 } // namespace rr

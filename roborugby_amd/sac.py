@@ -9,10 +9,11 @@ call handles all N arenas.
 Acting -- every row, every vector step -- is rr_sac_act where it applies (one HIP kernel: the hidden layers on the fp32 matrix cores, the
 draw, the squash; csrc/rr_sac.hip); anything else, and fused=False, goes through the torch modules.  Learning is PyTorch autograd on the
 same parameters (five small MLPs); with fused_targets=True its no-grad half -- the replay gathers, the policy sample, both critics on it and
-the target value net: value_target and q_hat -- is rr_sac_targets, one HIP kernel, and autograd keeps the backward passes.  No convergence
-claim is made for this trainer.
+the target value net: value_target and q_hat -- is rr_sac_targets, one HIP kernel, and autograd keeps the backward passes; with
+fused_grads=True the value net's and both critics' gradients come from rr_sac_grads (one fused kernel and its reduce), and autograd keeps
+the actor's backward alone.  No convergence claim is made for this trainer.
 
-    python -m roborugby_amd.sac --num-envs 65536 --steps 300 --preset T --checkpoint runs/sac_T.pt [--fused-targets]
+    python -m roborugby_amd.sac --num-envs 65536 --steps 300 --preset T --checkpoint runs/sac_T.pt [--fused-targets] [--fused-grads]
 """
 import argparse
 import copy
@@ -102,10 +103,14 @@ class BatchedSACAgent:
     fused_targets: True = learn() takes value_target and q_hat from rr_sac_targets (one launch on the rings; the value target's noise is
     then the kernel's draw under (seed, learn call) instead of a torch.randn from the agent's generator); needs what fused=True needs and
     batch_size % 64 == 0.  Default False.
+    fused_grads: True = the learn step takes the gradients of the value loss and the critic loss from rr_sac_grads (no autograd for the
+    value net and the critics; the actor loss and its backward stay autograd); needs what fused_targets needs, works with fused_targets
+    on or off.  Default False.
     The replay is a ring on the device with float actions [M, A], written with torch indexing for the rows whose `valid` is set."""
 
     def __init__(self, alpha=1e-4, beta=1e-4, input_dims=11, n_actions=2, max_action=1.0, gamma=.99, max_mem_size=1 << 20, tau=.005,
-                 fc1_dims=256, fc2_dims=256, batch_size=4096, reward_scale=2.0, device="cpu", seed=0, fused=None, fused_targets=False):
+                 fc1_dims=256, fc2_dims=256, batch_size=4096, reward_scale=2.0, device="cpu", seed=0, fused=None, fused_targets=False,
+                 fused_grads=False):
         self.gamma, self.tau, self.scale = gamma, tau, reward_scale
         self.n_actions, self.input_dims, self.max_action = int(n_actions), int(input_dims), float(max_action)
         self.mem_size, self.batch_size = int(max_mem_size), int(batch_size)
@@ -141,7 +146,12 @@ class BatchedSACAgent:
         if self.fused_targets and not (can_fuse and self.batch_size > 0 and self.batch_size % 64 == 0):
             raise ValueError("fused_targets=True needs a GPU, the reference's 11-256-256 networks, 2 or 4 actions and a batch_size that is a "
                              "positive multiple of 64")
-        self._dqn = _lib.DqnHandle(d) if self.fused or self.fused_targets else None
+        self.fused_grads = bool(fused_grads)
+        if self.fused_grads and not (can_fuse and self.batch_size > 0 and self.batch_size % 64 == 0):
+            raise ValueError("fused_grads=True needs a GPU, the reference's 11-256-256 networks, 2 or 4 actions and a batch_size that is a "
+                             "positive multiple of 64")
+        self._dqn = _lib.DqnHandle(d) if self.fused or self.fused_targets or self.fused_grads else None
+        self._grad_bufs = None  # rr_sac_grads' outputs: one tensor per parameter of value, critic_1, critic_2, and loss [3] (first use)
 
     # what dqn._train_result reads of an agent: SAC has no epsilon schedule, and its target follows every learn() (soft update)
     epsilon, target_update_freq = 0.0, 0
@@ -242,16 +252,39 @@ class BatchedSACAgent:
                               seed=self._seed, calls=self._learn_calls, state=state, action=action, **windows)
         return value_target, q_hat, state, action
 
+    def actor_loss(self, state, noise_actor):
+        """mean(log pi(a | s) - min(Q1, Q2)(s, a)) with a the reparameterised sample under noise_actor (:357-366)"""
+        actions, log_probs = self.actor.sample_normal(state, noise_actor, reparameterize=True)
+        critic_value = torch.min(self.critic_1(state, actions), self.critic_2(state, actions)).view(-1)
+        return torch.mean(log_probs - critic_value)
+
     def losses_given_targets(self, state, action, value_target, q_hat, noise_actor):
         """The autograd half of losses(): (value_loss, actor_loss, critic_loss) from the batch's states and actions, the two target
         vectors [B] (constants) and the standard normal tensor [B, A] of the reparameterised sample behind the actor loss."""
         value = self.value(state).view(-1)
         value_loss = 0.5 * F.mse_loss(value, value_target)
-        actions, log_probs = self.actor.sample_normal(state, noise_actor, reparameterize=True)
-        critic_value = torch.min(self.critic_1(state, actions), self.critic_2(state, actions)).view(-1)
-        actor_loss = torch.mean(log_probs - critic_value)
+        actor_loss = self.actor_loss(state, noise_actor)
         critic_loss = 0.5 * F.mse_loss(self.critic_1(state, action).view(-1), q_hat) + 0.5 * F.mse_loss(self.critic_2(state, action).view(-1), q_hat)
         return value_loss, actor_loss, critic_loss
+
+    @torch.no_grad()
+    def grads_fused(self, state, action, value_target, q_hat):
+        """The gradients of losses_given_targets()' value_loss and critic_loss through rr_sac_grads (no autograd): state [B, 11], action
+        [B, A], value_target, q_hat [B], dense float32 on the agent's device, B a multiple of 64 -> ((value, critic_1, critic_2): per
+        net one gradient tensor per parameter, in parameters() order), loss [3] = 0.5 * mse of value, critic_1, critic_2: value_loss =
+        loss[0], critic_loss = loss[1] + loss[2]).  The tensors are the agent's own buffers: the next call overwrites them."""
+        if self._dqn is None:
+            raise ValueError("grads_fused needs an agent built with fused, fused_targets or fused_grads on a GPU")
+        B, A = int(state.shape[0]), self.n_actions
+        nets = [list(n.parameters()) for n in (self.value, self.critic_1, self.critic_2)]
+        assert all(p.is_contiguous() and p.dtype == torch.float32 for n in nets for p in n)
+        for t, shape in ((state, (B, self.input_dims)), (action, (B, A)), (value_target, (B,)), (q_hat, (B,))):
+            assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == nets[0][0].device
+        if self._grad_bufs is None:
+            self._grad_bufs = ([[torch.empty_like(p) for p in n] for n in nets], torch.empty(3, device=self.device))
+        grads, loss = self._grad_bufs
+        self._dqn.sac_grads(*nets, state, action, value_target, q_hat, B, A, *grads, loss)
+        return tuple(grads), loss
 
     @torch.no_grad()
     def update_network_parameters(self, tau=None):
@@ -277,7 +310,7 @@ class BatchedSACAgent:
             self._learn_calls += 1
             value_target, q_hat, state, action = self.targets_fused(idx, mem_rows=max_mem)
             noise_actor = torch.randn((self.batch_size, self.n_actions), generator=self.gen, device=self.device)
-            return self._step(self.losses_given_targets(state, action, value_target, q_hat, noise_actor))
+            return self._learn_given_targets(state, action, value_target, q_hat, noise_actor)
         batch = (self.state_memory[idx], self.action_memory[idx], self.reward_memory[idx], self.new_state_memory[idx], self.terminal_memory[idx])
         shape = (self.batch_size, self.n_actions)
         noise_value = torch.randn(shape, generator=self.gen, device=self.device)
@@ -287,7 +320,33 @@ class BatchedSACAgent:
     def learn_on(self, batch, noise_value, noise_actor):
         """learn() after its draws, a function of the agent's state and its arguments alone: the losses of batch = (state, action, reward,
         new_state, done) under the two standard normal tensors [B, A], the value, actor and critic steps, the soft update, the counters."""
-        return self._step(self.losses(batch, noise_value, noise_actor))
+        value_target, q_hat = self.targets(batch, noise_value)
+        return self._learn_given_targets(batch[0], batch[1], value_target, q_hat, noise_actor)
+
+    def _learn_given_targets(self, state, action, value_target, q_hat, noise_actor):
+        """learn() after its targets: autograd of the three losses, or (fused_grads) of the actor loss alone next to rr_sac_grads"""
+        if self.fused_grads:
+            return self._step_fused_grads(state.contiguous(), action.contiguous(), value_target, q_hat, noise_actor)
+        return self._step(self.losses_given_targets(state, action, value_target, q_hat, noise_actor))
+
+    def _step_fused_grads(self, state, action, value_target, q_hat, noise_actor):
+        """_step() with fused_grads: the actor loss and its backward by autograd (inputs = the actor's parameters), the value net's and the
+        critics' gradients from ONE rr_sac_grads call into the agent's per-parameter buffers, installed as .grad; then the same three
+        steps in the reference's order, the soft update, the counters.  last_losses = (loss[0], actor_loss, loss[1] + loss[2])."""
+        actor_loss = self.actor_loss(state, noise_actor)
+        for opt in (self.value_optimizer, self.actor_optimizer, self.critic_optimizer):
+            opt.zero_grad(set_to_none=True)
+        actor_loss.backward(inputs=list(self.actor.parameters()))
+        grads, loss = self.grads_fused(state, action, value_target, q_hat)
+        for net, gs in zip((self.value, self.critic_1, self.critic_2), grads):
+            for p, g in zip(net.parameters(), gs):
+                p.grad = g
+        for opt in (self.value_optimizer, self.actor_optimizer, self.critic_optimizer):
+            opt.step()
+        self.update_network_parameters()
+        self.updates += 1
+        self.last_losses = (loss[0].clone(), actor_loss.detach(), loss[1] + loss[2])
+        return self.last_losses
 
     def _step(self, losses):
         """the value, actor and critic steps on their losses, the soft update, the counters"""
@@ -324,12 +383,12 @@ class BatchedSACAgent:
 
 def train_sac(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, checkpoint=None, resume=None, log_every=50, learn=True,
               mem_size=1 << 20, dtype="f64", updates_per_step=1, batch_size=4096, out=None, step_budget_clocks=0, fused=None,
-              fused_targets=False):
+              fused_targets=False, fused_grads=False):
     """The main loop of Training_SAC_pytorch.py over a batched env with action_mode="thrust": per vector step, serial on one stream,
     choose_action (rr_sac_act: one launch for every arena) -> env.step_thrust (the agent drives the happy team: A = 2 * nr_happy
     columns) -> remember the rows that were transitions (a row whose status has WAS_RESET was only re-placed and ends none) ->
-    updates_per_step x learn() (fused_targets: its no-grad half through rr_sac_targets).  Returns dqn.train()'s result dict (+ n_actions,
-    fused_act, fused_targets, mem_cntr, act_calls and the three losses).
+    updates_per_step x learn() (fused_targets: its no-grad half through rr_sac_targets; fused_grads: the value net's and the critics'
+    gradients through rr_sac_grads).  Returns dqn.train()'s result dict (+ n_actions, fused_act, fused_targets, fused_grads, mem_cntr, act_calls and the three losses).
     The budgeted step is not wired to this trainer: step_budget_clocks != 0 is refused."""
     import roborugby_amd as rr
     from .dqn import _save_checkpoint, _train_result, _write_result
@@ -339,7 +398,7 @@ def train_sac(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, ch
     A = env.action_space.shape[0]
     agent = BatchedSACAgent(input_dims=env.observation_space.shape[0], n_actions=A, max_action=float(env.action_space.high.max()),
                             max_mem_size=mem_size, batch_size=batch_size, device=device, seed=seed, fused=fused,
-                            fused_targets=fused_targets)
+                            fused_targets=fused_targets, fused_grads=fused_grads)
     if resume:
         ck = torch.load(resume, map_location=device)
         agent.load_state_dict(ck["agent"])
@@ -374,7 +433,8 @@ def train_sac(num_envs=65536, steps=300, preset="T", device="cuda:0", seed=0, ch
     res = _train_result(agent, env, num_envs * steps, dt, steps, int(real_rows.item()), 0, updates_per_step if learn else 0, num_envs, False,
                         0.0, 0.0, False, float(score_sum.mean() / max(steps, 1)), preset, dtype, [])
     ls = [float(x) for x in agent.last_losses] if agent.last_losses else [None] * 3
-    res.update(mode="train_sac", n_actions=A, fused_act=bool(agent.fused), fused_targets=bool(agent.fused_targets), mem_cntr=agent.mem_cntr,
+    res.update(mode="train_sac", n_actions=A, fused_act=bool(agent.fused), fused_targets=bool(agent.fused_targets), fused_grads=bool(agent.fused_grads),
+               mem_cntr=agent.mem_cntr,
                act_calls=agent._act_calls,
                tau=agent.tau, reward_scale=agent.scale, value_loss=ls[0], actor_loss=ls[1], critic_loss=ls[2], resumed_from=resume)
     agent.close()
@@ -401,10 +461,12 @@ def main():
     ap.add_argument("--no-fused", action="store_true", help="choose_action through the torch modules instead of rr_sac_act")
     ap.add_argument("--fused-targets", action="store_true",
                     help="learn()'s no-grad half (replay gathers, policy sample, critics, target value net) through rr_sac_targets")
+    ap.add_argument("--fused-grads", action="store_true",
+                    help="the value net's and the critics' gradients through rr_sac_grads (the actor's backward stays autograd)")
     a = ap.parse_args()
     res = train_sac(a.num_envs, a.steps, a.preset, a.device, a.seed, a.checkpoint, a.resume, a.log_every, not a.no_learn,
                     updates_per_step=a.updates_per_step, batch_size=a.batch_size, out=a.out, fused=False if a.no_fused else None,
-                    fused_targets=a.fused_targets)
+                    fused_targets=a.fused_targets, fused_grads=a.fused_grads)
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
 
 
